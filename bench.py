@@ -5,7 +5,7 @@ driver records), plus the two other measured configurations of BASELINE.json in 
 shape: --config 4 (CWT morlet, 84 scales, 1000 x 10 s @ 44.1 kHz) and --config 5 (CQT 84 bins +
 chroma, 30 s @ 44.1 kHz clips, 125 clips per GPU).
 
-    python bench.py --gpus 1 --steps K --warmup W [--config 2|4|5]
+    python bench.py --gpus 1 --steps K --warmup W [--config 2|4|5] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -31,6 +31,9 @@ exposed_ms (step time beyond the step's own compute) and overlap_hidden_ms.
 `dense_bank` (same line): the dense filter-bank route north_star names as the MFMA path -- gammatone-128 at the headline shape as
 frames/s with its own oracle check, and the route's product alone (k_gemm_bank_bf16x3, one chunk's shape) as bf16 matrix FLOP/s
 against the 2.5 PF/s dense peak (`roofline.bound` "mfma"); mfma_busy is replayed from profiles/r06_rocprofv3_dense.txt.
+--dump-outputs DIR: once the K timed steps are fenced, what step K - 1 left for the caller goes to DIR/<name>.npy in float32 (cfg 2: mel,
+mfcc; cfg 4: cwt_real, cwt_imag of the step's last call; cfg 5: cqt_real, cqt_imag, chroma), at most 64 MB in all -- beyond that a fixed
+seeded choice of rows.  The inputs are seeded, so two builds given the same arguments write comparable files.
 `cpu_baseline` times the reference's own C path (oracle/_ref, built-in FFT + naive
 double-accumulating matmul: no FFTW/MKL in this image) on the host cores for a bounded sample.
 """
@@ -214,6 +217,9 @@ class Cfg2:
     def slab(self, i, which):
         return self.cc[i & 1] if which == "mfcc" else self.mel
 
+    def result(self, i):
+        return {"mel": self.mel, "mfcc": self.cc[i & 1]}
+
     def check(self, i):
         from oracle import ref
         if not ref.available():
@@ -270,6 +276,12 @@ class Cfg4:
             self.o.cwt_device(self.x[c0:c0 + n], re[:n], im[:n])
             k += 1
         self.last = (k - 1) & 1, self.units - n, n
+
+    def result(self, i):
+        # (the ring keeps the step's last device call only: its n chunks)
+        slot, _, n = self.last
+        re, im = self.ring[slot]
+        return {"cwt_real": re[:n], "cwt_imag": im[:n]}
 
     def check(self, i):
         from oracle import ref
@@ -330,6 +342,9 @@ class Cfg5:
     def slab(self, i, which):
         return self.ch[i & 1] if which == "chroma" else self.re
 
+    def result(self, i):
+        return {"cqt_real": self.re, "cqt_imag": self.im, "chroma": self.ch[i & 1]}
+
     def check(self, i):
         from oracle import ref
         if not ref.available():
@@ -376,6 +391,9 @@ class DryRun:
     def slab(self, i, which):
         return self.cc[i & 1] if which == self.small else self.wide
 
+    def result(self, i):
+        return {"small": self.cc[i & 1], "wide": self.wide}
+
     def check(self, i):
         return None
 
@@ -401,6 +419,29 @@ def pmc_traffic(config, clips):
     return None, None
 
 
+DUMP_BYTES = 63 * 10**6  # --dump-outputs promises 64 MB in all: the arrays' share, the .npy headers stay inside the rest
+
+
+def dump_outputs(torch, path, arrays):
+    """--dump-outputs: each tensor of `arrays` (name -> what the step left for the caller) as <path>/<name>.npy, float32.  Together over
+    DUMP_BYTES, every array keeps the same share of its rows (leading dimensions flattened), chosen by a fixed seed from the row count alone:
+    the same rows for every build and run of the same command line, and for arrays with equally many rows (mel / mfcc of one frame).
+    Returns what was written, for the JSON line."""
+    os.makedirs(path, exist_ok=True)
+    keep = DUMP_BYTES / sum(4 * t.numel() for t in arrays.values())
+    rec = {}
+    for name, t in arrays.items():
+        n = t.numel() // t.shape[-1]
+        if keep < 1.0:
+            k = max(1, int(n * keep))
+            rows = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+            t = t.reshape(n, t.shape[-1])[torch.from_numpy(rows).to(t.device)]
+        a = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        rec[name] = {"shape": list(a.shape), "rows_of": n}
+    return rec
+
+
 class CpuEvent:
     """stand-in for torch.cuda.Event in the dry run"""
     def __init__(self, enable_timing=True):
@@ -413,10 +454,11 @@ class CpuEvent:
         return (other.t - self.t) * 1e3
 
 
-def measure(w, torch, dist, dev, world, steps, warmup, clock_warmup, sustained_s, gathers=(), which=(), dry=False):
+def measure(w, torch, dist, dev, world, steps, warmup, clock_warmup, sustained_s, gathers=(), which=(), dry=False, dump_dir=None):
     """W untimed steps, then exactly `steps` steps between barrier + synchronize fences; the steps' average device time from
     ONE pair of events on the launch stream around them; optionally a back-to-back loop of >= sustained_s seconds.  With `gathers` the slabs
-    of step i travel to rank 0 on a side stream while step i + 1 computes (double-buffered sources)."""
+    of step i travel to rank 0 on a side stream while step i + 1 computes (double-buffered sources).  With `dump_dir` the results of the last
+    timed step are written there behind the closing fence, before anything else runs (dump_outputs)."""
     Event = CpuEvent if dry else torch.cuda.Event
     sync = (lambda: None) if dry else torch.cuda.synchronize
     comm = torch.cuda.Stream(device=dev) if (gathers and not dry) else None
@@ -483,7 +525,8 @@ def measure(w, torch, dist, dev, world, steps, warmup, clock_warmup, sustained_s
     res = {"elapsed": elapsed, "last": max(steps - 1, 0),
            "kern_ms": float(ev[0][0].elapsed_time(ev[0][1]) / steps) if ev else None,
            "gather_ms": float(np.mean([g0.elapsed_time(g1) for g0, g1 in gev])) if gev else None,
-           "sustained_ms": None, "clock": None}
+           "sustained_ms": None, "clock": None,
+           "dumped": dump_outputs(torch, dump_dir, w.result(steps - 1)) if dump_dir else None}
     # ---- outside the timed region: the shader clock THIS device holds under THIS workload (a sleeping wave on a side stream
     # samples s_memtime against the constant reference clock while the steps below run on the other CUs: afx_clock_probe_start)
     probe = None
@@ -731,7 +774,12 @@ def main():
     ap.add_argument("--clock-warmup", type=float, default=0.5, help="seconds of untimed steps before the W warm-up "
                     "steps: the device ramps its clocks over tens of ms after idling, and W steps of ~1.5 ms end "
                     "long before that (0 disables; reported as config.clock_warmup_s)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last of them computed (rank 0's "
+                    "arrays, as a caller receives them) to DIR/<name>.npy, float32, at most 64 MB in all: beyond that a fixed seeded "
+                    "choice of rows")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps: the rate is units x steps / the time of exactly that many steps, so at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: no launcher environment, so this process becomes the launcher -- the same
@@ -773,7 +821,7 @@ def main():
     gathers = ([afd.FeatureGather(dst=0, counts=counts) for _ in which] if (world > 1 and not a.no_gather) else [])
 
     m = measure(w, torch, dist, dev, world, a.steps, a.warmup, a.clock_warmup,
-                0.0 if a.no_sustained else 1.0, gathers, which, dry)
+                0.0 if a.no_sustained else 1.0, gathers, which, dry, a.dump_outputs if rank == 0 else None)
     elapsed = m["elapsed"]
 
     # ---- outside the timed region ----------------------------------------------------------------
@@ -815,6 +863,8 @@ def main():
             "roofline": roofline(W, w, clips, m),
             "oracle_check": {"clip0_max_rel_err": err, "bar": 1e-5},
         }
+        if m["dumped"]:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "of_step": a.steps - 1, "arrays": m["dumped"]}
         if a.total_clips > 0:
             out["config"]["total_clips"], out["config"]["clips_per_rank"] = a.total_clips, counts
         if world > 1:
