@@ -156,8 +156,8 @@ typedef struct {
     long long outStride;
 } AfxIstftArgs;
 int afxk_istft(const AfxIstftArgs *a, void *stream);
-/* n_fft 2048: one wave per frame (the inverse as ONE forward real transform of re + im of the Hermitian part), overlap-add in an
- * LDS ring, no frame scratch (a->frames / a->twiddle are not read); AFX_ERR_UNSUPPORTED: not its case -- run afxk_istft */
+/* n_fft 256 ... 4096: one wave per frame (the inverse as ONE forward real transform of re + im of the Hermitian part), overlap-add
+ * in an LDS ring, no frame scratch (a->frames / a->twiddle are not read); AFX_ERR_UNSUPPORTED: not its case -- run afxk_istft */
 int afxk_istft_fused(const AfxIstftArgs *a, void *stream);
 
 /* afx_spectral.hip: per-bin value (AFX_SPEC_*) of the bins [binLo, binLo+binCount) of a complex
@@ -464,14 +464,39 @@ typedef struct {
     float *energy, *rms, *zcr; /* device [batch*timeLength]: temporal features of the windowed frame */
 } AfxMelFusedArgs;
 
-/* variant index able to run (radix2Exp, tapsA, tapsB), or -1 */
+/* One plan type and one create / run / destroy for the four transform sizes (afx_melfused.hip, afx_melplan.h); every size
+ * (n_fft 512: afx_melfused512.hip, 1024: afx_melfused1k.hip, 2048: afx_melfused2.hip, 4096: afx_melfused4k2.hip) contributes
+ * its tap variants, its table-fill function and its launchers.
+ * afxk_melfused_variant: index into the size's variant table able to run (tapsA, tapsB), or -1 */
 int afxk_melfused_variant(int radix2Exp, int tapsA, int tapsB);
 int afxk_melfused_create(void **plan, int radix2Exp, const float *hWindow,
                          const AfxBandPlan *band, void *stream);
 int afxk_melfused_run(void *plan, const AfxMelFusedArgs *a, void *stream);
 void afxk_melfused_destroy(void *plan);
-/* 0: no plan, 1: rows in whole slots, 2: split plan (row segments); 101: the n_fft 1024 kernel; 201 / 202: the n_fft 4096 kernel, whole rows / split plan */
+/* 0: no plan; otherwise 1: rows in whole slots, 2: split plan (row segments), plus the size's base -- 0 at n_fft 2048,
+ * 100 at 1024, 200 at 4096, 300 at 512 (bftObj_fusedPlanKind: 1 / 2, 101 / 102, 201 / 202, 301 / 302) */
 int afxk_melfused_kind(const void *plan);
+
+/* How the fused kernels and their STFT instantiations spread `total` frames over the device: `rounds` rounds of workgroups
+ * of `wavesPerWg` waves (one workgroup is resident per CU), every wave a contiguous run of *framesPerWave frames; returns
+ * the workgroups to launch (0: nothing to do).  Long runs per wave (register re-use of the overlapping frames) once a round
+ * of workgroups is full -- 1 / 2 / 3 rounds measure the same at the headline size (1.558 / 1.559 / 1.559 ms per step), 6
+ * rounds + 1.2 %, two keep the tail short.  A call that cannot fill one round with 16-frame runs -- the one-clip legacy
+ * entry points: 1000 frames -- is spread over all CUs instead (16 frames in sequence per wave were 75 us of a 1000-frame
+ * call's 190, profiles/r05_legacy_phases.txt).  Shared with the host tests (tests/test_bandplan.py). */
+static inline long long afx_frame_split(long long total, int cus, int wavesPerWg, int rounds, long long *framesPerWave) {
+    *framesPerWave = 0;
+    if (total <= 0) return 0;
+    const long long oneRoundWaves = (long long)cus * wavesPerWg, waves = oneRoundWaves * rounds;
+    long long fpw = (total + waves - 1) / waves;
+    if (fpw < 16) {
+        const long long oneRound = (total + oneRoundWaves - 1) / oneRoundWaves;
+        fpw = oneRound < 16 ? oneRound : 16;
+    }
+    const long long usedWaves = (total + fpw - 1) / fpw;
+    *framesPerWave = fpw;
+    return (usedWaves + wavesPerWg - 1) / wavesPerWg;
+}
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,6 @@
 
 #include <cstdint>
 #include <cstdlib>
-#include <mutex>
 
 #include "afx_device.h"
 #include "afx_hipcheck.h"
@@ -661,26 +660,7 @@ int resident_groups(size_t lds, int waves) {
 // twiddle tables of the small wave transforms, one device copy per device and size (never freed)
 template <class F>
 const float2 *small_tables() {
-    static std::mutex mu;
-    static float2 *dTab[AFX_MAX_DEVICES] = {};
-    const int dev = afxdev_current_device();
-    if (dev < 0 || dev >= AFX_MAX_DEVICES) return nullptr;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!dTab[dev]) {
-        float *h = static_cast<float *>(calloc(2 * F::TAB_F2, sizeof(float)));
-        if (!h) return nullptr;
-        F::fill_tables(h);
-        float2 *d = nullptr;
-        int st = afxdev_malloc(reinterpret_cast<void **>(&d), sizeof(float) * 2 * F::TAB_F2);
-        if (st == AFX_OK && hipMemcpy(d, h, sizeof(float) * 2 * F::TAB_F2, hipMemcpyHostToDevice) != hipSuccess) st = AFX_ERR_HIP;
-        free(h);
-        if (st != AFX_OK) {
-            afxdev_free(d);
-            return nullptr;
-        }
-        dTab[dev] = d;
-    }
-    return dTab[dev];
+    return reinterpret_cast<const float2 *>(afx_device_table<F::fill_tables>(sizeof(float) * 2 * F::TAB_F2));
 }
 
 template <class F>

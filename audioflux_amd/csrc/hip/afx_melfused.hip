@@ -1,95 +1,61 @@
-// afx_melfused.hip -- fused STFT -> filter bank, one 64-lane wave per frame: plan management and dispatch by transform
-// size.  n_fft 2048 runs k_stft_mel_v2 (afx_melfused2.hip) for real AND complex results (bftObj_setResultType(0), the
-// reference wrapper's default: bft_algorithm.c:457-485; round 1's separate complex-result kernel of this file is gone since
-// the complex instantiations of k_stft_mel_v2 keep three waves per SIMD); n_fft 1024 / 4096 live in afx_melfused1k.hip /
-// afx_melfused4k2.hip, n_fft 512 in afx_melfused512.hip.
+// afx_melfused.hip -- fused STFT -> filter bank, one 64-lane wave per frame: the ONE host plan layer of the four transform
+// sizes.  Plan, band-plan packing, create / destroy, plan kinds and the size-independent argument checks live here; a size
+// contributes an AfxMelSize (afx_melplan.h): its tap variants, its table-fill function and its launchers -- n_fft 512
+// afx_melfused512.hip, 1024 afx_melfused1k.hip, 2048 afx_melfused2.hip (real AND complex results: bftObj_setResultType(0), the
+// reference wrapper's default, bft_algorithm.c:457-485), 4096 afx_melfused4k2.hip.  The device pieces the four kernels share
+// are in afx_melparts.h.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
 
-#include "afx_device.h"
-#include "afx_hipcheck.h"
+#include "afx_melplan.h"
 
 namespace {
 
-struct Plan {
-    int variant;  // first field of every size's plan: < 100 this file (n_fft 2048), >= 100 afx_melfused1k, >= 200 afx_melfused4k2, >= 300 afx_melfused512
-    int num;
-    int split;  // slots hold row segments (AfxBandPlan.split)
-    void *v2;   // plan of afx_melfused2.hip
-};
+const AfxMelSize *size_of(int radix2Exp) {
+    switch (radix2Exp) {
+        case 9: return afx_mel_size512();
+        case 10: return afx_mel_size1k();
+        case 11: return afx_mel_size2k();
+        case 12: return afx_mel_size4k();
+        default: return nullptr;
+    }
+}
 
-struct Variant {
-    int tapsA, tapsB;
-};
-constexpr Variant kVariants[] = {{48, 16}, {72, 32}};
-constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
+// AfxBandPlan -> the lane-weight block wL [64][WP] (A taps, then at TA the B taps of variant (TA, TB)) and meta[384]
+void pack_band(const AfxBandPlan *band, int TA, int WP, float *wL, int *meta) {
+    for (int l = 0; l < 64; ++l) {
+        for (int t = 0; t < band->tapsA; ++t) wL[(size_t)l * WP + t] = band->wA[(size_t)t * 64 + l];
+        for (int t = 0; t < band->tapsB; ++t) wL[(size_t)l * WP + TA + t] = band->wB[(size_t)t * 64 + l];
+        meta[l] = band->startA[l];
+        meta[64 + l] = band->startB[l];
+        meta[128 + l] = band->rowA[l];
+        meta[192 + l] = band->rowB[l];
+        meta[256 + l] = (int)band->segIdx[l];
+        meta[320 + l] = (int)band->segIdx[64 + l];
+    }
+}
 
 }  // namespace
 
-// n_fft = 2048: afx_melfused2.hip
-extern "C" int afxk_mel2_create(void **plan, int variant, const float *hWindow, const AfxBandPlan *band, void *stream);
-extern "C" int afxk_mel2_run(void *plan, const AfxMelFusedArgs *a, void *stream);
-extern "C" void afxk_mel2_destroy(void *plan);
-
-// n_fft = 1024 lives in afx_melfused1k.hip; its plans carry variant numbers >= 100
-extern "C" int afxk_mel1k_variant(int tapsA, int tapsB);
-extern "C" int afxk_mel1k_create(void **plan, const float *hWindow, const AfxBandPlan *band, void *stream);
-extern "C" int afxk_mel1k_run(void *plan, const AfxMelFusedArgs *a, void *stream);
-extern "C" void afxk_mel1k_destroy(void *plan);
-extern "C" int afxk_mel1k_kind(const void *plan);
-
-// n_fft = 512 lives in afx_melfused512.hip (variant numbers >= 300)
-extern "C" int afxk_mel512_variant(int tapsA, int tapsB);
-extern "C" int afxk_mel512_create(void **plan, const float *hWindow, const AfxBandPlan *band, void *stream);
-extern "C" int afxk_mel512_run(void *plan, const AfxMelFusedArgs *a, void *stream);
-extern "C" void afxk_mel512_destroy(void *plan);
-extern "C" int afxk_mel512_kind(const void *plan);
-
-// n_fft = 4096 lives in afx_melfused4k2.hip (variant numbers 200 .. 299)
-extern "C" int afxk_mel4k_variant(int tapsA, int tapsB);
-extern "C" int afxk_mel4k_create(void **plan, const float *hWindow, const AfxBandPlan *band, void *stream);
-extern "C" int afxk_mel4k_run(void *plan, const AfxMelFusedArgs *a, void *stream);
-extern "C" void afxk_mel4k_destroy(void *plan);
-extern "C" int afxk_mel4k_kind(const void *plan);
-
 extern "C" int afxk_melfused_variant(int radix2Exp, int tapsA, int tapsB) {
-    if (afxdev_no_fused()) return -1;
-    if (radix2Exp == 9) return afxk_mel512_variant(tapsA, tapsB);
-    if (radix2Exp == 10) return afxk_mel1k_variant(tapsA, tapsB);
-    if (radix2Exp == 12) return afxk_mel4k_variant(tapsA, tapsB);
-    if (radix2Exp != 11) return -1;
-    for (int i = 0; i < kNumVariants; ++i) {
-        if (tapsA <= kVariants[i].tapsA && tapsB <= kVariants[i].tapsB) return i;
-    }
+    const AfxMelSize *s = size_of(radix2Exp);
+    if (afxdev_no_fused() || !s) return -1;
+    for (int i = 0; i < s->numVariants; ++i)
+        if (tapsA <= s->variants[i].tapsA && tapsB <= s->variants[i].tapsB) return i;
     return -1;
 }
 
 extern "C" int afxk_melfused_kind(const void *plan) {
-    const Plan *p = static_cast<const Plan *>(plan);
-    if (!p) return 0;
-    if (p->variant >= 300) return afxk_mel512_kind(plan);
-    if (p->variant >= 200) return afxk_mel4k_kind(plan);
-    if (p->variant >= 100) return afxk_mel1k_kind(plan);
-    return p->split ? 2 : 1;
+    const AfxMelPlan *p = static_cast<const AfxMelPlan *>(plan);
+    return !p ? 0 : size_of(p->radix2Exp)->kindBase + (p->split ? 2 : 1);
 }
 
 extern "C" void afxk_melfused_destroy(void *plan) {
-    Plan *p = static_cast<Plan *>(plan);
+    AfxMelPlan *p = static_cast<AfxMelPlan *>(plan);
     if (!p) return;
-    if (p->variant >= 300) {
-        afxk_mel512_destroy(plan);
-        return;
-    }
-    if (p->variant >= 200) {
-        afxk_mel4k_destroy(plan);
-        return;
-    }
-    if (p->variant >= 100) {
-        afxk_mel1k_destroy(plan);
-        return;
-    }
-    afxk_mel2_destroy(p->v2);
+    afxdev_free(p->dTab);
+    afxdev_free(p->dMeta);
     free(p);
 }
 
@@ -98,15 +64,30 @@ extern "C" int afxk_melfused_create(void **plan, int radix2Exp, const float *hWi
     *plan = nullptr;
     const int variant = afxk_melfused_variant(radix2Exp, band->tapsA, band->tapsB);
     if (variant < 0) return AFX_ERR_UNSUPPORTED;
-    if (variant >= 300) return afxk_mel512_create(plan, hWindow, band, stream);
-    if (variant >= 200) return afxk_mel4k_create(plan, hWindow, band, stream);
-    if (variant >= 100) return afxk_mel1k_create(plan, hWindow, band, stream);
-    Plan *p = static_cast<Plan *>(calloc(1, sizeof(Plan)));
-    if (!p) return AFX_ERR_NOMEM;
+    const AfxMelSize *s = size_of(radix2Exp);
+    const int TA = s->variants[variant].tapsA, TB = s->variants[variant].tapsB;
+    const int WP = TA + TB + 4;
+    const size_t bytes = (size_t)s->bandOff + (size_t)64 * WP * 4;
+    AfxMelPlan *p = static_cast<AfxMelPlan *>(calloc(1, sizeof(AfxMelPlan)));
+    float *tab = static_cast<float *>(calloc(bytes, 1));
+    if (!p || !tab) {
+        free(p);
+        free(tab);
+        return AFX_ERR_NOMEM;
+    }
+    p->radix2Exp = radix2Exp;
     p->variant = variant;
     p->num = band->num;
     p->split = band->split;
-    const int st = afxk_mel2_create(&p->v2, variant, hWindow, band, stream);
+    s->fill(tab, hWindow);
+    int meta[384];
+    pack_band(band, TA, WP, tab + s->bandOff / 4, meta);
+    int st = afxdev_malloc(reinterpret_cast<void **>(&p->dTab), bytes);
+    if (st == AFX_OK) st = afxdev_h2d(p->dTab, tab, bytes, stream);
+    if (st == AFX_OK) st = afxdev_malloc(reinterpret_cast<void **>(&p->dMeta), sizeof(meta));
+    if (st == AFX_OK) st = afxdev_h2d(p->dMeta, meta, sizeof(meta), stream);
+    if (st == AFX_OK) st = afxdev_stream_sync(stream);  // host staging buffers are freed below
+    free(tab);
     if (st != AFX_OK) {
         afxk_melfused_destroy(p);
         return st;
@@ -115,11 +96,12 @@ extern "C" int afxk_melfused_create(void **plan, int radix2Exp, const float *hWi
     return AFX_OK;
 }
 
+// specMap 0 / 1 / 2: real results, 3 / 4: complex results (out + outIm); AFX_ERR_UNSUPPORTED when the requested fusion
+// (cepstra / temporal features) does not apply to this plan
 extern "C" int afxk_melfused_run(void *plan, const AfxMelFusedArgs *a, void *stream) {
-    const Plan *p = static_cast<const Plan *>(plan);
+    const AfxMelPlan *p = static_cast<const AfxMelPlan *>(plan);
     if (!p) return AFX_ERR_ARG;
-    if (p->variant >= 300) return afxk_mel512_run(plan, a, stream);
-    if (p->variant >= 200) return afxk_mel4k_run(plan, a, stream);
-    if (p->variant >= 100) return afxk_mel1k_run(plan, a, stream);
-    return afxk_mel2_run(p->v2, a, stream);  // real and complex results
+    if (a->energy && p->radix2Exp != 11) return AFX_ERR_UNSUPPORTED;  // temporal features ride along at n_fft 2048 only (cepstra: every size)
+    if (a->specMap > 4) return AFX_ERR_ARG;
+    return size_of(p->radix2Exp)->run(p, a, stream);
 }

@@ -10,17 +10,13 @@
 // flux_vector.c:55-86).
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 
-#include "afx_device.h"
-#include "afx_hipcheck.h"
-#include "afx_pkmath.h"
+#include "afx_melplan.h"
+#include "afx_melparts.h"
 #include "afx_ccblock.h"
 
 #ifndef AFX_CC_GROUPS  // whole-row plans: 16-band groups of the rows requested per trip to the L2, and whether the next trip is requested ahead
@@ -29,10 +25,6 @@
 #endif
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ v2 lo2(v4f q) { return v2{q.x, q.y}; }
-__device__ __forceinline__ v2 hi2(v4f q) { return v2{q.z, q.w}; }
 
 constexpr int NFFT = 1024;
 constexpr int MC = 512;            // complex FFT length
@@ -80,50 +72,6 @@ struct KArgs {
     int ccNum, ccCbrt;
     float *cc;             // [totalFrames, ccNum]
 };
-
-// what an STFT instantiation stores for a spectrum value (the maps of afx_stft.hip)
-__device__ __forceinline__ void stft_map(float re, float im, int mode, float normValue, float &v0, float &v1) {
-    v1 = 0.f;
-    switch (mode) {
-        case AFX_SPEC_COMPLEX: v0 = re; v1 = im; break;
-        case AFX_SPEC_POWER: v0 = re * re + im * im; break;
-        case AFX_SPEC_MAG: v0 = sqrtf(re * re + im * im); break;
-        case AFX_SPEC_SQUARE: v0 = re * re - im * im; v1 = 2.f * re * im; break;
-        case AFX_SPEC_MAG_NORM: v0 = powf(sqrtf(re * re + im * im), normValue); break;
-        case AFX_SPEC_PHASE: v0 = atan2f(im, re < 1e-16f ? 1e-16f : re); break;
-        default: v0 = powf(re * re + im * im, normValue); break;  // AFX_SPEC_POWER_NORM
-    }
-}
-
-// |X|^2 of the conjugate pair (k, 512-k) from A = Z[k], B = Z[512-k], w = 0.5 W_1024^k
-__device__ __forceinline__ void split_pair(v2 A, v2 B, v2 w, float &pk, float &pq) {
-    const v2 e2 = pk_add_conj(A, B);
-    const v2 d = pk_sub_conj(A, B);
-    const v2 wo = cmul_mi(d, w);
-    const v2 x = e2 * 0.5f + wo;  // X[k]
-    const v2 y = e2 * 0.5f - wo;  // conj(X[512-k])
-    pk = x.x * x.x + x.y * x.y;
-    pq = y.x * y.x + y.y * y.y;
-}
-__device__ __forceinline__ void split_pair_c(v2 A, v2 B, v2 w, bool sq, float &kr, float &ki, float &qr,
-                                             float &qi) {
-    const v2 e2 = pk_add_conj(A, B);
-    const v2 d = pk_sub_conj(A, B);
-    const v2 wo = cmul_mi(d, w);
-    const v2 x = e2 * 0.5f + wo;
-    const v2 y = e2 * 0.5f - wo;
-    if (sq) {
-        kr = x.x * x.x - x.y * x.y;
-        ki = 2.f * (x.x * x.y);
-        qr = y.x * y.x - y.y * y.y;
-        qi = -2.f * (y.x * y.y);
-    } else {
-        kr = x.x;
-        ki = x.y;
-        qr = y.x;
-        qi = -y.y;
-    }
-}
 
 // STFT: no bank -- the spectrum values themselves (CPLX form) go to memory through stft_map (the STFT object's full complex
 //   spectrum, linear-scale bin slices: afxk_stft1k, afx_melfused4k2.hip has the same at n_fft 4096); MAPPED: any AFX_SPEC_* map,
@@ -336,12 +284,12 @@ __global__ __launch_bounds__(WAVES * 64) void k_stft_band_1k(KArgs a) {
                 PIN(w3[j]);
                 // k = 0 pairs with itself (X[0] and X[512]); lane 0's read of slot 512 is past the image and discarded
                 const v2 zbj = (j == 0) ? (lane0 ? za[0] : zb[0]) : zb[j];
-                if (CPLX) split_pair_c(za[j], zbj, w3[j], !STFT && a.specMap == 4, pk[j], pkI[CPLX ? j : 0], pq[j], pqI[CPLX ? j : 0]);
+                if (CPLX) split_pair_cmap(za[j], zbj, w3[j], !STFT && a.specMap == 4, pk[j], pkI[CPLX ? j : 0], pq[j], pqI[CPLX ? j : 0]);
                 else split_pair(za[j], zbj, w3[j], pk[j], pq[j]);
             }
             PIN(zm);
             PIN(wm);
-            if (CPLX) split_pair_c(zm, zm, wm, !STFT && a.specMap == 4, pk[4], pkI[CPLX ? 4 : 0], pq[4], pqI[CPLX ? 4 : 0]);
+            if (CPLX) split_pair_cmap(zm, zm, wm, !STFT && a.specMap == 4, pk[4], pkI[CPLX ? 4 : 0], pq[4], pqI[CPLX ? 4 : 0]);
             else split_pair(zm, zm, wm, pk[4], pq[4]);
         }
         if (CPLX) {
@@ -410,8 +358,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_stft_band_1k(KArgs a) {
             if (lane0) prow[256] = pk[4];
             wave_lds_order();
 
-            // ---- 4. banded filter bank: weights by ds_read_b128, power row by immediate-offset ds_read_b64; the NEXT
-            //         block of four quads is requested before this block's values are waited for (see afx_melfused2.hip)
+            // ---- 4. banded filter bank: band_stage of afx_melparts.h, kept in place -- hoisted into the header's template it
+            //         compiles to a different register allocation in this kernel (BLK = 2 for complex results)
             float accA, accB;
             {
                 constexpr int QA = TA / 4, QB = TB / 4, QT = QA + QB, BLK = CPLX ? 2 : 4, NB = (QT + BLK - 1) / BLK;  // (complex: ten values wait for the second pass)
@@ -458,9 +406,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_stft_band_1k(KArgs a) {
                             sB += hi2(w[cur][i]) * p1[cur][i];
                         }
                     }
-                    // the sums of this block before the next block's requests: left free, the scheduler sinks every
-                    // multiply-add behind the last request and keeps all the operands alive (212-532 bytes of scratch per lane)
-                    PIN(sA);
+                    PIN(sA);  // (this block's sums before the next block's requests: band_stage, afx_melparts.h)
                     PIN(sB);
                 }
                 accA = sA.x + sA.y;
@@ -521,9 +467,12 @@ __global__ __launch_bounds__(WAVES * 64) void k_stft_band_1k(KArgs a) {
     }
 }
 
-// host: W_512^(lane d0) | W_64^(c d1) | 0.5 W_1024^k (k <= 256), in double, rounded once
-void fill_twiddles(float *tw1, float *tw2, float *tw3) {
+// host: the blob in the kernel's LDS layout -- window (w[2n], w[2n+1]) | W_512^(lane d0) | W_64^(c d1) | 0.5 W_1024^k (k <= 256);
+// twiddles in double, rounded once; hWindow == nullptr leaves the window part alone
+void fill_transform_tables(float *tab, const float *hWindow) {
     const double PI = 3.14159265358979323846;
+    float *tw1 = tab + T_TW1 / 4, *tw2 = tab + T_TW2 / 4, *tw3 = tab + T_TW3 / 4;
+    if (hWindow) memcpy(tab + T_WIN / 4, hWindow, sizeof(float) * NFFT);
     for (int d = 0; d < 8; ++d)
         for (int l = 0; l < 64; ++l) {
             const double ang = -2.0 * PI * (double)(d * l) / MC;
@@ -543,38 +492,24 @@ void fill_twiddles(float *tw1, float *tw2, float *tw3) {
     }
 }
 
-struct Plan {
-    int variant;  // >= 100: this file (afxk_melfused_* dispatches on it)
-    int num, split;
-    float2 *dWin2, *dTw1, *dTw2, *dTw3;
-    float *dWLane;
-    int *dMeta;
-};
-struct Variant {
-    int tapsA, tapsB;
-};
 // ordered by cost; the plan's conflict-free lane assignment can stretch the short rows of a
 // dense low band (mel-128 at n_fft 1024: 23 / 25 taps), hence the square variant
-constexpr Variant kVariants[] = {{24, 8}, {32, 32}, {48, 16}, {72, 32}};
-constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
+constexpr AfxMelVariant kVariants[] = {{24, 8}, {32, 32}, {48, 16}, {72, 32}};
+
+// the kernel takes its tables by pointer: the parts of one blob in the LDS layout (window: a plan's own, or the STFT object's)
+void set_tables(KArgs &k, const float *tab) {
+    k.win2 = reinterpret_cast<const float2 *>(tab + T_WIN / 4);
+    k.tw1 = reinterpret_cast<const float2 *>(tab + T_TW1 / 4);
+    k.tw2 = reinterpret_cast<const float2 *>(tab + T_TW2 / 4);
+    k.tw3 = reinterpret_cast<const float2 *>(tab + T_TW3 / 4);
+}
 
 template <int TA, int TB, bool GENERAL, int SHIFT, bool CPLX, bool SPLIT = false, bool CC = false>
-int launch_variant(const Plan *p, const AfxMelFusedArgs *a, void *stream) {
+int launch_variant(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
     const long long total = (long long)a->batch * a->timeLength;
     if (total <= 0) return AFX_OK;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    long long waves = (long long)cus * WAVES * 2;
-    long long fpw = (total + waves - 1) / waves;
-    // long runs per wave (register re-use of the overlapping frames) once a round of workgroups is full; a call that
-    // cannot fill one round -- the one-clip legacy entry points: 1000 frames -- is spread over all CUs instead
-    // (16 frames in sequence per wave were 75 us of a 1000-frame call's 190, profiles/r05_legacy_phases.txt)
-    if (fpw < 16) {
-        const long long oneRound = (total + (long long)cus * WAVES - 1) / ((long long)cus * WAVES);
-        fpw = oneRound < 16 ? oneRound : 16;
-    }
-    const long long usedWaves = (total + fpw - 1) / fpw;
-    const long long blocks = (usedWaves + WAVES - 1) / WAVES;
+    long long fpw;
+    const long long blocks = afx_mel_frames(total, WAVES, &fpw);
     KArgs k;
     k.x = a->x;
     k.clipStride = a->clipStride;
@@ -583,11 +518,8 @@ int launch_variant(const Plan *p, const AfxMelFusedArgs *a, void *stream) {
     k.hop = a->hop;
     k.framesPerWave = (int)fpw;
     k.aligned = ((a->clipStride & 1) == 0) && ((a->hop & 1) == 0) && ((reinterpret_cast<uintptr_t>(a->x) & 7) == 0);
-    k.win2 = p->dWin2;
-    k.tw1 = p->dTw1;
-    k.tw2 = p->dTw2;
-    k.tw3 = p->dTw3;
-    k.wLane = p->dWLane;
+    set_tables(k, p->dTab);
+    k.wLane = p->dTab + TAB_BYTES / 4;
     k.meta = p->dMeta;
     k.specMap = a->specMap;
     k.postPow = a->postPow;
@@ -601,21 +533,13 @@ int launch_variant(const Plan *p, const AfxMelFusedArgs *a, void *stream) {
     k.cc = a->cc;
     constexpr size_t lds = (size_t)block_lds_bytes(TA, TB) + (CC ? CCB_BYTES : 0);  // (CC: the DCT operand table behind the wave regions)
     static_assert(lds <= 163840, "workgroup LDS budget");
-    static std::atomic<bool> attrSet[AFX_MAX_DEVICES];  // per device: the attribute lives in the device's code object
-    const int attrDev = afxdev_current_device() & (AFX_MAX_DEVICES - 1);
-    if (!attrSet[attrDev].load(std::memory_order_acquire)) {  // (two threads may both set it: idempotent)
-        AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_stft_band_1k<TA, TB, GENERAL, SHIFT, CPLX, false, false, false, SPLIT, CC>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attrSet[attrDev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((k_stft_band_1k<TA, TB, GENERAL, SHIFT, CPLX, false, false, false, SPLIT, CC>), dim3((unsigned)blocks), dim3(WAVES * 64), lds,
-                       (hipStream_t)stream, k);
+    AFX_LAUNCH_DYN_LDS((k_stft_band_1k<TA, TB, GENERAL, SHIFT, CPLX, false, false, false, SPLIT, CC>), dim3((unsigned)blocks), dim3(WAVES * 64), lds, stream, k);
     AFX_LAUNCH_CHECK("k_stft_band_1k");
     return AFX_OK;
 }
 
 template <int TA, int TB>
-int launch(const Plan *p, const AfxMelFusedArgs *a, void *stream) {
+int launch(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
     const bool general = (a->specMap != 0) || a->postPow;
     const bool shift2 = (a->hop == 256);  // hop = 128 * SHIFT
     if (a->cc) {  // cepstra in the same launch: real results, plain power rows on whole-row plans, every real mode on split plans
@@ -646,142 +570,33 @@ int launch(const Plan *p, const AfxMelFusedArgs *a, void *stream) {
                   : launch_variant<TA, TB, false, 0, false>(p, a, stream);
 }
 
-template <typename T>
-int upload(T **dptr, const void *src, size_t bytes, void *stream) {
-    int st = afxdev_malloc(reinterpret_cast<void **>(dptr), bytes);
-    if (st != AFX_OK) return st;
-    return afxdev_h2d(*dptr, src, bytes, stream);
+int run(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
+    switch (p->variant) {
+        case 0: return launch<24, 8>(p, a, stream);
+        case 1: return launch<32, 32>(p, a, stream);
+        case 2: return launch<48, 16>(p, a, stream);
+        case 3: return launch<72, 32>(p, a, stream);
+        default: return AFX_ERR_UNSUPPORTED;
+    }
 }
 
 }  // namespace
 
-extern "C" int afxk_mel1k_variant(int tapsA, int tapsB) {
-    for (int i = 0; i < kNumVariants; ++i)
-        if (tapsA <= kVariants[i].tapsA && tapsB <= kVariants[i].tapsB) return 100 + i;
-    return -1;
-}
-
-extern "C" int afxk_mel1k_kind(const void *plan) {
-    const Plan *p = static_cast<const Plan *>(plan);
-    return !p ? 0 : (p->split ? 102 : 101);
-}
-
-extern "C" void afxk_mel1k_destroy(void *plan) {
-    Plan *p = static_cast<Plan *>(plan);
-    if (!p) return;
-    afxdev_free(p->dWin2);
-    afxdev_free(p->dTw1);
-    afxdev_free(p->dTw2);
-    afxdev_free(p->dTw3);
-    afxdev_free(p->dWLane);
-    afxdev_free(p->dMeta);
-    free(p);
-}
-
-extern "C" int afxk_mel1k_create(void **plan, const float *hWindow, const AfxBandPlan *band, void *stream) {
-    *plan = nullptr;
-    const int variant = afxk_mel1k_variant(band->tapsA, band->tapsB);
-    if (variant < 0) return AFX_ERR_UNSUPPORTED;
-    const int TA = kVariants[variant - 100].tapsA, TB = kVariants[variant - 100].tapsB;
-    Plan *p = static_cast<Plan *>(calloc(1, sizeof(Plan)));
-    if (!p) return AFX_ERR_NOMEM;
-    p->variant = variant;
-    p->num = band->num;
-    p->split = band->split;
-    const int WP = TA + TB + 4;
-    float *tw1 = static_cast<float *>(malloc(sizeof(float) * 2 * TAB_TW1_F2));
-    float *tw2 = static_cast<float *>(malloc(sizeof(float) * 2 * TAB_TW2_F2));
-    float *tw3 = static_cast<float *>(calloc(2 * TAB_TW3_F2, sizeof(float)));
-    float *wL = static_cast<float *>(calloc((size_t)64 * WP, sizeof(float)));
-    int meta[384];  // startA | startB | rowA | rowB | segIdx[0..63] | segIdx[64..127]
-    int st = (tw1 && tw2 && tw3 && wL) ? AFX_OK : AFX_ERR_NOMEM;
-    if (st == AFX_OK) {
-        fill_twiddles(tw1, tw2, tw3);
-        for (int l = 0; l < 64; ++l) {
-            for (int t = 0; t < band->tapsA; ++t) wL[(size_t)l * WP + t] = band->wA[(size_t)t * 64 + l];
-            for (int t = 0; t < band->tapsB; ++t) wL[(size_t)l * WP + TA + t] = band->wB[(size_t)t * 64 + l];
-            meta[l] = band->startA[l];
-            meta[64 + l] = band->startB[l];
-            meta[128 + l] = band->rowA[l];
-            meta[192 + l] = band->rowB[l];
-            meta[256 + l] = (int)band->segIdx[l];
-            meta[320 + l] = (int)band->segIdx[64 + l];
-        }
-        st = upload(&p->dWin2, hWindow, sizeof(float) * NFFT, stream);
-    }
-    if (st == AFX_OK) st = upload(&p->dTw1, tw1, sizeof(float) * 2 * TAB_TW1_F2, stream);
-    if (st == AFX_OK) st = upload(&p->dTw2, tw2, sizeof(float) * 2 * TAB_TW2_F2, stream);
-    if (st == AFX_OK) st = upload(&p->dTw3, tw3, sizeof(float) * 2 * TAB_TW3_F2, stream);
-    if (st == AFX_OK) st = upload(&p->dWLane, wL, sizeof(float) * (size_t)64 * WP, stream);
-    if (st == AFX_OK) st = upload(&p->dMeta, meta, sizeof(meta), stream);
-    if (st == AFX_OK) st = afxdev_stream_sync(stream);
-    free(tw1);
-    free(tw2);
-    free(tw3);
-    free(wL);
-    if (st != AFX_OK) {
-        afxk_mel1k_destroy(p);
-        return st;
-    }
-    *plan = p;
-    return AFX_OK;
-}
-
-extern "C" int afxk_mel1k_run(void *plan, const AfxMelFusedArgs *a, void *stream) {
-    if (a->energy) return AFX_ERR_UNSUPPORTED;  // temporal features ride along at n_fft 2048 only (cepstra: every size, launch())
-    const Plan *p = static_cast<const Plan *>(plan);
-    if (!p) return AFX_ERR_ARG;
-    switch (p->variant) {
-        case 100: return launch<24, 8>(p, a, stream);
-        case 101: return launch<32, 32>(p, a, stream);
-        case 102: return launch<48, 16>(p, a, stream);
-        case 103: return launch<72, 32>(p, a, stream);
-        default: return AFX_ERR_UNSUPPORTED;
-    }
+const AfxMelSize *afx_mel_size1k() {
+    static const AfxMelSize size = {10, 100, kVariants, 4, TAB_BYTES, fill_transform_tables, run};
+    return &size;
 }
 
 // ---- n_fft 1024 without a bank (afxk_stft, afx_stft.hip): every frame inside its clip (no padding), no temporal features.
 namespace {
 
-// twiddle tables of the STFT instantiations, one device copy per device, never freed: tw1 | tw2 | tw3
-const float2 *stft_tables(void *stream) {
-    static std::mutex mu;
-    static float2 *dTab[AFX_MAX_DEVICES] = {};
-    const int dev = afxdev_current_device();
-    if (dev < 0 || dev >= AFX_MAX_DEVICES) return nullptr;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!dTab[dev]) {
-        constexpr int NF2 = TAB_TW1_F2 + TAB_TW2_F2 + TAB_TW3_F2;
-        float *h = static_cast<float *>(calloc(2 * NF2, sizeof(float)));
-        if (!h) return nullptr;
-        fill_twiddles(h, h + 2 * TAB_TW1_F2, h + 2 * (TAB_TW1_F2 + TAB_TW2_F2));
-        float2 *d = nullptr;
-        int st = afxdev_malloc(reinterpret_cast<void **>(&d), sizeof(float) * 2 * NF2);
-        // (a synchronous copy, like wave_tables() of afx_stft.hip: the caller's stream is not waited for under this lock)
-        if (st == AFX_OK && hipMemcpy(d, h, sizeof(float) * 2 * NF2, hipMemcpyHostToDevice) != hipSuccess) st = AFX_ERR_HIP;
-        free(h);
-        if (st != AFX_OK) {
-            afxdev_free(d);
-            return nullptr;
-        }
-        dTab[dev] = d;
-    }
-    return dTab[dev];
-}
+void fill_stft_tables(float *tab) { fill_transform_tables(tab, nullptr); }  // the twiddle blob of the STFT instantiations (afx_device_table)
 
 template <int SHIFT, bool MAPPED, bool FULL>
-int launch_stft(const AfxStftArgs *a, const float2 *tab, void *stream) {
+int launch_stft(const AfxStftArgs *a, const float *tab, void *stream) {
     const long long total = (long long)a->batch * a->timeLength;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    long long waves = (long long)cus * WAVES * 2;
-    long long fpw = (total + waves - 1) / waves;
-    if (fpw < 16) {
-        const long long oneRound = (total + (long long)cus * WAVES - 1) / ((long long)cus * WAVES);
-        fpw = oneRound < 16 ? oneRound : 16;
-    }
-    const long long usedWaves = (total + fpw - 1) / fpw;
-    const long long blocks = (usedWaves + WAVES - 1) / WAVES;
+    long long fpw;
+    const long long blocks = afx_mel_frames(total, WAVES, &fpw);
     KArgs k;
     memset(&k, 0, sizeof(k));
     k.x = a->x;
@@ -791,10 +606,8 @@ int launch_stft(const AfxStftArgs *a, const float2 *tab, void *stream) {
     k.hop = a->hop;
     k.framesPerWave = (int)fpw;
     k.aligned = ((a->clipStride & 1) == 0) && ((a->hop & 1) == 0) && ((reinterpret_cast<uintptr_t>(a->x) & 7) == 0);
+    set_tables(k, tab);
     k.win2 = reinterpret_cast<const float2 *>(a->window);  // (w[2n], w[2n+1]) at [n]: the object's window as it lies
-    k.tw1 = tab;
-    k.tw2 = tab + TAB_TW1_F2;
-    k.tw3 = tab + TAB_TW1_F2 + TAB_TW2_F2;
     k.specMap = 3;
     k.normValue = a->normValue;
     k.out = a->outRe;
@@ -804,15 +617,7 @@ int launch_stft(const AfxStftArgs *a, const float2 *tab, void *stream) {
     k.binCount = a->binCount;
     k.outPitch = a->outPitch ? a->outPitch : (long long)a->binCount;
     constexpr size_t lds = (size_t)block_lds_bytes(0, 0);
-    static std::atomic<bool> attrSet[AFX_MAX_DEVICES];
-    const int attrDev = afxdev_current_device() & (AFX_MAX_DEVICES - 1);
-    if (!attrSet[attrDev].load(std::memory_order_acquire)) {  // (two threads may both set it: idempotent)
-        AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_stft_band_1k<0, 0, false, SHIFT, true, true, MAPPED, FULL>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attrSet[attrDev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((k_stft_band_1k<0, 0, false, SHIFT, true, true, MAPPED, FULL>), dim3((unsigned)blocks), dim3(WAVES * 64), lds,
-                       (hipStream_t)stream, k);
+    AFX_LAUNCH_DYN_LDS((k_stft_band_1k<0, 0, false, SHIFT, true, true, MAPPED, FULL>), dim3((unsigned)blocks), dim3(WAVES * 64), lds, stream, k);
     AFX_LAUNCH_CHECK("k_stft_band_1k<stft>");
     return AFX_OK;
 }
@@ -828,7 +633,7 @@ extern "C" int afxk_stft1k(const AfxStftArgs *a, void *stream) {
     const bool two = (a->mode == AFX_SPEC_COMPLEX || a->mode == AFX_SPEC_SQUARE);
     if (!a->outRe || (two && !a->outIm)) return AFX_ERR_ARG;
     if ((long long)a->batch * a->timeLength <= 0) return AFX_OK;
-    const float2 *tab = stft_tables(stream);
+    const float *tab = afx_device_table<fill_stft_tables>(TAB_BYTES);
     if (!tab) return AFX_ERR_UNSUPPORTED;
     const bool s2 = a->hop == 256;  // register re-use of the overlapping frames
     if (a->mode == AFX_SPEC_COMPLEX) {

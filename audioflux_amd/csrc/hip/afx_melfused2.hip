@@ -30,35 +30,13 @@
 // Index algebra and LDS bank behaviour of every access class: tools/proto_fft1024_v2.py.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-#include <mutex>
-
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 
-#include "afx_device.h"
-#include "afx_hipcheck.h"
-#include "afx_pkmath.h"
+#include "afx_melplan.h"
+#include "afx_melparts.h"  // (also the knock-out switches AFX_KO of the measurement builds: RD128_S ... KO_ON)
 #include "afx_ccblock.h"
-
-// Knock-out measurement builds (make EXTRA=-DAFX_KO=<mask>; results are WRONG, timing only): bit s drops the LDS traffic of
-// site class s -- 0 exchange writes, 1 exchange / image reads, 2 table reads (window, twiddles), 3 band-stage reads, 4 power-row
-// writes -- and leaves the arithmetic on whatever the registers hold; bit 5 drops the second radix-16 layer's arithmetic,
-// bit 6 the band-stage multiply-adds.  What the step time does NOT lose says what does not bind it (profiles/r05_ab_headline.txt (c)).
-#ifdef AFX_KO
-#define KO_ON(s) (((AFX_KO) >> (s)) & 1)
-#define RD128_S(s, dst, addr, off) do { if (KO_ON(s)) asm volatile("" : "=v"(dst)); else RD128(dst, addr, off); } while (0)
-#define RD64_S(s, dst, addr, off) do { if (KO_ON(s)) asm volatile("" : "=v"(dst)); else RD64(dst, addr, off); } while (0)
-#define WR2_64_S(s, addr, d0, d1, o0, o1) do { if (KO_ON(s)) asm volatile("" ::"v"(d0), "v"(d1)); else WR2_64(addr, d0, d1, o0, o1); } while (0)
-#define WR2ST_32_S(s, addr, d0, d1, o0, o1) do { if (KO_ON(s)) asm volatile("" ::"v"(d0), "v"(d1)); else WR2ST_32(addr, d0, d1, o0, o1); } while (0)
-#else
-#define KO_ON(s) 0
-#define RD128_S(s, dst, addr, off) RD128(dst, addr, off)
-#define RD64_S(s, dst, addr, off) RD64(dst, addr, off)
-#define WR2_64_S(s, addr, d0, d1, o0, o1) WR2_64(addr, d0, d1, o0, o1)
-#define WR2ST_32_S(s, addr, d0, d1, o0, o1) WR2ST_32(addr, d0, d1, o0, o1)
-#endif
 
 // measurement switches of round 6 (profiles/r06_ab_headline.txt): AFX_V2_NTIN -- the samples are read with the streaming (nt) policy, so
 // that the bank rows a wave re-reads for its cepstra 16 frames later are not pushed out of the L2 by them; AFX_V2_CCEVERY -- frames per
@@ -74,8 +52,6 @@
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 constexpr int NFFT = 2048;
 constexpr int MC = 1024;
 constexpr int WAVES = 12;                    // one workgroup per CU, 3 waves per SIMD (8: - 5 %, profiles/r02_ab_headline.txt)
@@ -86,7 +62,7 @@ constexpr int PROW_OFF = 5120;               // byte offset of the power row in 
 constexpr int PROW_F = 1104;                 // 1025 bins + zero pad for the fixed-length band loops
 constexpr int WAVE_LDS = PROW_OFF + PROW_F * 4;  // 9536: pad [9220, 9536) lies behind both images
 static_assert(16 * P1 * 8 <= PROW_OFF + 1025 * 4, "exchange image must end before the zero pad");
-// table blob, byte offsets (built on the host by afxk_mel2_create, copied to LDS per workgroup)
+// table blob, byte offsets (built on the host by fill_tables + afxk_melfused_create, copied to LDS per workgroup)
 constexpr int T_WIN = 0;                     // [8][64] float4: (w[2n], w[2n+1]) of rows n1 = 2j, 2j + 1
 constexpr int T_TW1 = 8192;                  // [8][64] float4: W_1024^(lane k1), k1 = 2j, 2j + 1
 constexpr int T_TW2 = 16384;                 // [4] rows of 16 float2, TW2_PITCH bytes apart: W_64^(m2 j1)
@@ -128,15 +104,8 @@ struct KArgs2 {
     int vecOut;            // binLo == 0, all 1025 bins, 16-byte aligned rows of >= 1028 floats: 16-byte stores (the pad gets zeros)
 };
 
-// (lds_addr, RD64 / RD128, WR2_64, WR2ST_32, PIN, LDS_WAIT_N and the L1-bypassing load: afx_asm.h)
-
-// Orders this wave's LDS stores before its later LDS loads of other lanes' data: DS operations of
-// one wave execute in issue order, lgkmcnt(0) drains them, the wave barrier pins the compiler.
-// Deliberately NOT a fence (that would also drain vmcnt: the prefetch and the previous stores).
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-}
+// (lds_addr, RD64 / RD128, WR2_64, WR2ST_32, PIN, LDS_WAIT_N and the L1-bypassing load: afx_asm.h; wave_lds_sync, split_pair,
+// split_pair_c, cplx_map, lo2 / hi2: afx_melparts.h)
 
 // Wave priority by phase of the frame (s_setprio): phases 0 window, 1 first radix-16 + twiddles + exchange writes, 2 exchange
 // reads, 3 second radix-16, 4 last radix-4 + split, 5 band, 6 store / cepstra; bit p of AFX_PRIO_MASK raises phase p to
@@ -154,34 +123,6 @@ __device__ __forceinline__ void wave_lds_sync() {
     do {                                                                                                   \
         if (AFX_PRIO_MASK != 0) __builtin_amdgcn_s_setprio(((AFX_PRIO_MASK >> (p)) & 1) ? AFX_PRIO_LEVEL : 0); \
     } while (0)
-
-__device__ __forceinline__ v2 lo2(v4f q) { return v2{q.x, q.y}; }
-__device__ __forceinline__ v2 hi2(v4f q) { return v2{q.z, q.w}; }
-
-// |X|^2 of the conjugate pair (k, 1024-k) from A = Z[k], B = Z[1024-k], w = 0.5 W_2048^k
-__device__ __forceinline__ void split_pair(v2 A, v2 B, v2 w, float &pk, float &pq) {
-    const v2 e2 = pk_add_conj(A, B);   // 2 E
-    const v2 d = pk_sub_conj(A, B);    // 2 i O
-    const v2 wo = cmul_mi(d, w);       // W O
-    const v2 x = e2 * 0.5f + wo;       // X[k]
-    const v2 y = e2 * 0.5f - wo;       // conj(X[1024-k])
-    pk = x.x * x.x + x.y * x.y;
-    pq = y.x * y.x + y.y * y.y;
-}
-
-// complex results: the spectrum values themselves, x = X[k], y = conj(X[1024-k])
-__device__ __forceinline__ void split_pair_c(v2 A, v2 B, v2 w, v2 &x, v2 &y) {
-    const v2 e2 = pk_add_conj(A, B);
-    const v2 d = pk_sub_conj(A, B);
-    const v2 wo = cmul_mi(d, w);
-    x = e2 * 0.5f + wo;
-    y = e2 * 0.5f - wo;
-}
-// (re, im) of the requested complex result from a spectrum value c: S (sq = false) or S^2 (bft_algorithm.c:457-485)
-__device__ __forceinline__ void cplx_map(v2 c, bool sq, float &re, float &im) {
-    re = sq ? c.x * c.x - c.y * c.y : c.x;
-    im = sq ? 2.f * (c.x * c.y) : c.y;
-}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -216,7 +157,7 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
         float4 *s4 = reinterpret_cast<float4 *>(smem);
         for (int i = threadIdx.x + (STFT ? T_TW1 / 16 : 0); i < TABB / 16; i += NWV * 64) s4[i] = a.tab[i];
         if constexpr (STFT) {
-            // the caller's window in the pair layout of afxk_mel2_create: entry (n1, lane) = (w[2n], w[2n+1]), n = 64 n1 + lane,
+            // the caller's window in the pair layout of fill_tables: entry (n1, lane) = (w[2n], w[2n+1]), n = 64 n1 + lane,
             // at float2 index 128 (n1 >> 1) + 2 lane + (n1 & 1)
             v2 *tw = reinterpret_cast<v2 *>(smem + T_WIN);
             const v2 *w2 = reinterpret_cast<const v2 *>(a.win);
@@ -602,58 +543,8 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
         //         block of four quads is requested before this block's values are waited for --------
         float accA, accB;
         {
-            constexpr int QA = TA / 4, QB = TB / 4, QT = QA + QB, BLK = 4, NB = (QT + BLK - 1) / BLK;
-            v2 sA = {0.f, 0.f}, sB = {0.f, 0.f};
-            v4f w[2][BLK];
-            v2 p0[2][BLK], p1[2][BLK];
-            auto request = [&](int blk, v4f (&wq)[BLK], v2 (&q0v)[BLK], v2 (&q1v)[BLK]) {
-#pragma unroll
-                for (int i = 0; i < BLK; ++i) {
-                    const int q = blk * BLK + i;
-                    if (q >= QT) continue;
-                    RD128_S(3, wq[i], awr, 16 * q);
-                    if (q < QA) {
-                        RD64_S(3, q0v[i], bpa, 16 * q);
-                        RD64_S(3, q1v[i], bpa, 16 * q + 8);
-                    } else {
-                        RD64_S(3, q0v[i], bpb, 16 * (q - QA));
-                        RD64_S(3, q1v[i], bpb, 16 * (q - QA) + 8);
-                    }
-                }
-            };
-            request(0, w[0], p0[0], p1[0]);
-#pragma unroll
-            for (int blk = 0; blk < NB; ++blk) {
-                const int cur = blk & 1;
-                const int nextQuads = (blk + 1 < NB) ? ((QT - (blk + 1) * BLK) < BLK ? (QT - (blk + 1) * BLK) : BLK) : 0;
-                if (blk + 1 < NB) request(blk + 1, w[cur ^ 1], p0[cur ^ 1], p1[cur ^ 1]);
-                if (nextQuads == 4) LDS_WAIT_N(12);
-                else if (nextQuads == 3) LDS_WAIT_N(9);
-                else if (nextQuads == 2) LDS_WAIT_N(6);
-                else if (nextQuads == 1) LDS_WAIT_N(3);
-                else LDS_WAIT_N(0);
-#pragma unroll
-                for (int i = 0; i < BLK; ++i) {
-                    if (blk * BLK + i >= QT) continue;
-                    PIN(w[cur][i]);
-                    PIN(p0[cur][i]);
-                    PIN(p1[cur][i]);
-                    const int q = blk * BLK + i;
-                    if (KO_ON(6)) {
-                        asm volatile("" ::"v"(w[cur][i]), "v"(p0[cur][i]), "v"(p1[cur][i]));
-                    } else if (q < QA) {
-                        sA += lo2(w[cur][i]) * p0[cur][i];
-                        sA += hi2(w[cur][i]) * p1[cur][i];
-                    } else {
-                        sB += lo2(w[cur][i]) * p0[cur][i];
-                        sB += hi2(w[cur][i]) * p1[cur][i];
-                    }
-                }
-                if constexpr (CPLX) {  // this block's sums before the next block's requests: left free, the multiply-adds of the
-                    PIN(sA);           // complex instantiations sink behind the last request with every operand alive (240-256
-                    PIN(sB);           // registers + 264 bytes of scratch -> 182)
-                }
-            }
+            v2 sA, sB;
+            band_stage<TA, TB, 4, CPLX>(awr, bpa, bpb, sA, sB);
             accA = sA.x + sA.y;
             accB = sB.x + sB.y;
         }
@@ -744,36 +635,15 @@ void fill_tables(float *tab, const float *hWindow) {
             }
 }
 
-struct Plan2 {
-    int variant, num, split;
-    float4 *dTab;
-    int *dMeta;
-};
-struct Variant {
-    int tapsA, tapsB;
-};
-constexpr Variant kVariants[] = {{48, 16}, {72, 32}};
+constexpr AfxMelVariant kVariants[] = {{48, 16}, {72, 32}};
 
 template <int TA, int TB, int SHIFT, bool SPLIT, int CC, bool TEMPORAL, bool CPLX = false>
-int launch_variant(const Plan2 *p, const AfxMelFusedArgs *a, void *stream) {
+int launch_variant(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
     const long long total = (long long)a->batch * a->timeLength;
     if (total <= 0) return AFX_OK;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    // one 12-wave workgroup is resident per CU; two rounds of workgroups keep the tail short while each
-    // wave still streams a long contiguous run of frames (and re-uses 3/4 of every frame from registers)
     constexpr int NWV = waves_of(CPLX);
-    long long waves = (long long)cus * NWV * 2;  // 1 / 2 / 3 rounds measure the same (1.558 / 1.559 / 1.559 ms), 6: +1.2 %
-    long long fpw = (total + waves - 1) / waves;
-    // long runs per wave (register re-use of the overlapping frames) once a round of workgroups is full; a call that
-    // cannot fill one round -- the one-clip legacy entry points: 1000 frames -- is spread over all CUs instead
-    // (16 frames in sequence per wave were 75 us of a 1000-frame call's 190, profiles/r05_legacy_phases.txt)
-    if (fpw < 16) {
-        const long long oneRound = (total + (long long)cus * NWV - 1) / ((long long)cus * NWV);
-        fpw = oneRound < 16 ? oneRound : 16;
-    }
-    const long long usedWaves = (total + fpw - 1) / fpw;
-    const long long blocks = (usedWaves + NWV - 1) / NWV;
+    long long fpw;
+    const long long blocks = afx_mel_frames(total, NWV, &fpw);
 
     KArgs2 k;
     memset(&k, 0, sizeof(k));
@@ -784,7 +654,7 @@ int launch_variant(const Plan2 *p, const AfxMelFusedArgs *a, void *stream) {
     k.hop = a->hop;
     k.framesPerWave = (int)fpw;
     k.aligned = ((a->clipStride & 1) == 0) && ((a->hop & 1) == 0) && ((reinterpret_cast<uintptr_t>(a->x) & 7) == 0);
-    k.tab = p->dTab;
+    k.tab = reinterpret_cast<const float4 *>(p->dTab);
     k.meta = p->dMeta;
     k.specMap = a->specMap;
     k.postPow = a->postPow;
@@ -801,21 +671,13 @@ int launch_variant(const Plan2 *p, const AfxMelFusedArgs *a, void *stream) {
     k.zcr = a->zcr;
     constexpr size_t lds = (size_t)block_lds_bytes(TA, TB, CC == 1);
     static_assert(lds <= 163840, "workgroup LDS budget");
-    static std::atomic<bool> attrSet[AFX_MAX_DEVICES];  // per device: the attribute lives in the device's code object
-    const int attrDev = afxdev_current_device() & (AFX_MAX_DEVICES - 1);
-    if (!attrSet[attrDev].load(std::memory_order_acquire)) {  // (two threads may both set it: idempotent)
-        AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_stft_mel_v2<TA, TB, SHIFT, SPLIT, CC, TEMPORAL, CPLX>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attrSet[attrDev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((k_stft_mel_v2<TA, TB, SHIFT, SPLIT, CC, TEMPORAL, CPLX>), dim3((unsigned)blocks), dim3(NWV * 64), lds,
-                       (hipStream_t)stream, k);
+    AFX_LAUNCH_DYN_LDS((k_stft_mel_v2<TA, TB, SHIFT, SPLIT, CC, TEMPORAL, CPLX>), dim3((unsigned)blocks), dim3(NWV * 64), lds, stream, k);
     AFX_LAUNCH_CHECK("k_stft_mel_v2");
     return AFX_OK;
 }
 
 template <int TA, int TB, bool SPLIT, int CC, bool TEMPORAL>
-int launch_hop(const Plan2 *p, const AfxMelFusedArgs *a, void *stream) {
+int launch_hop(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
     // register re-use of the overlapping frames for hop = 128 * SHIFT: N/8, N/4, N/2
 #ifdef AFX_EXPERIMENTS  // measurement builds only (make EXTRA=-DAFX_EXPERIMENTS): AFX_EXP_MEL=noshift fetches every frame whole
     if (const char *e = getenv("AFX_EXP_MEL"))
@@ -830,7 +692,7 @@ int launch_hop(const Plan2 *p, const AfxMelFusedArgs *a, void *stream) {
 }
 
 template <int TA, int TB>
-int launch(const Plan2 *p, const AfxMelFusedArgs *a, void *stream) {
+int launch(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
     const bool cc = a->cc != nullptr, tmp = a->energy != nullptr;
     if (a->specMap >= 3) {  // complex results: S (3) or S^2 (4); hop N/4 with register re-use, any other hop plain
         if (cc || tmp) return AFX_ERR_UNSUPPORTED;
@@ -861,46 +723,17 @@ int launch(const Plan2 *p, const AfxMelFusedArgs *a, void *stream) {
                     : launch_hop<TA, TB, false, 0, false>(p, a, stream);
 }
 
-// twiddle tables of the STFT instantiations (the blob without window and bank), one device copy per device, never freed
-const float4 *stft2k_tables() {
-    static std::mutex mu;
-    static float4 *dTab[AFX_MAX_DEVICES] = {};
-    const int dev = afxdev_current_device();
-    if (dev < 0 || dev >= AFX_MAX_DEVICES) return nullptr;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!dTab[dev]) {
-        const size_t bytes = (size_t)tab_bytes(0, 0);
-        float *h = static_cast<float *>(calloc(bytes, 1));
-        if (!h) return nullptr;
-        fill_tables(h, nullptr);
-        float4 *d = nullptr;
-        int st = afxdev_malloc(reinterpret_cast<void **>(&d), bytes);
-        // (a synchronous copy: the caller's stream is not waited for under this lock)
-        if (st == AFX_OK && hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) != hipSuccess) st = AFX_ERR_HIP;
-        free(h);
-        if (st != AFX_OK) {
-            afxdev_free(d);
-            return nullptr;
-        }
-        dTab[dev] = d;
-    }
-    return dTab[dev];
+int run(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
+    return p->variant == 0 ? launch<48, 16>(p, a, stream) : launch<72, 32>(p, a, stream);
 }
 
+void fill_stft_tables(float *tab) { fill_tables(tab, nullptr); }  // the twiddle blob of the STFT instantiations (afx_device_table)
+
 template <int SHIFT>
-int launch_stft2k(const AfxStftArgs *a, const float4 *tab, void *stream) {
+int launch_stft2k(const AfxStftArgs *a, const float *tab, void *stream) {
     const long long total = (long long)a->batch * a->timeLength;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    // the frame distribution of launch_variant: two rounds of 12-wave workgroups, short calls spread over every CU
-    long long waves = (long long)cus * WAVES * 2;
-    long long fpw = (total + waves - 1) / waves;
-    if (fpw < 16) {
-        const long long oneRound = (total + (long long)cus * WAVES - 1) / ((long long)cus * WAVES);
-        fpw = oneRound < 16 ? oneRound : 16;
-    }
-    const long long usedWaves = (total + fpw - 1) / fpw;
-    const long long blocks = (usedWaves + WAVES - 1) / WAVES;
+    long long fpw;
+    const long long blocks = afx_mel_frames(total, WAVES, &fpw);
     KArgs2 k;
     memset(&k, 0, sizeof(k));
     k.x = a->x;
@@ -910,7 +743,7 @@ int launch_stft2k(const AfxStftArgs *a, const float4 *tab, void *stream) {
     k.hop = a->hop;
     k.framesPerWave = (int)fpw;
     k.aligned = ((a->clipStride & 1) == 0) && ((a->hop & 1) == 0) && ((reinterpret_cast<uintptr_t>(a->x) & 7) == 0);
-    k.tab = tab;
+    k.tab = reinterpret_cast<const float4 *>(tab);
     k.specMap = a->mode == AFX_SPEC_POWER ? 0 : a->mode == AFX_SPEC_MAG ? 1 : 2;
     k.normValue = a->normValue;
     k.out = a->outRe;
@@ -921,20 +754,17 @@ int launch_stft2k(const AfxStftArgs *a, const float4 *tab, void *stream) {
     k.vecOut = a->binLo == 0 && a->binCount == NFFT / 2 + 1 && k.outPitch >= 1028 && (k.outPitch & 3) == 0 &&
                (reinterpret_cast<uintptr_t>(a->outRe) & 15) == 0;
     constexpr size_t lds = (size_t)block_lds_bytes(0, 0, false);
-    static std::atomic<bool> attrSet[AFX_MAX_DEVICES];
-    const int attrDev = afxdev_current_device() & (AFX_MAX_DEVICES - 1);
-    if (!attrSet[attrDev].load(std::memory_order_acquire)) {
-        AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_stft_mel_v2<0, 0, SHIFT, false, 0, false, false, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attrSet[attrDev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((k_stft_mel_v2<0, 0, SHIFT, false, 0, false, false, true>), dim3((unsigned)blocks), dim3(WAVES * 64), lds,
-                       (hipStream_t)stream, k);
+    AFX_LAUNCH_DYN_LDS((k_stft_mel_v2<0, 0, SHIFT, false, 0, false, false, true>), dim3((unsigned)blocks), dim3(WAVES * 64), lds, stream, k);
     AFX_LAUNCH_CHECK("k_stft_mel_v2 (stft)");
     return AFX_OK;
 }
 
 }  // namespace
+
+const AfxMelSize *afx_mel_size2k() {
+    static const AfxMelSize size = {11, 0, kVariants, 2, T_BAND, fill_tables, run};
+    return &size;
+}
 
 // The n_fft 2048 wave transform storing its mapped spectrum rows (real results: |S|^2, |S|, |S|^2p) -- the [T, F] rows of the
 // dense-bank route and of the STFT / linear-scale objects (stft_algorithm.c:717-803, bft_algorithm.c:489-504); every frame inside
@@ -949,7 +779,7 @@ extern "C" int afxk_stft2k(const AfxStftArgs *a, void *stream) {
     const long long total = (long long)a->batch * a->timeLength;
     if (total <= 0) return AFX_OK;
     if (total > 0x7fffffffLL) return AFX_ERR_UNSUPPORTED;
-    const float4 *tab = stft2k_tables();
+    const float *tab = afx_device_table<fill_stft_tables>((size_t)tab_bytes(0, 0));
     if (!tab) return AFX_ERR_UNSUPPORTED;
     switch (a->hop) {
         case 256: return launch_stft2k<2>(a, tab, stream);
@@ -957,66 +787,4 @@ extern "C" int afxk_stft2k(const AfxStftArgs *a, void *stream) {
         case 1024: return launch_stft2k<8>(a, tab, stream);
         default: return launch_stft2k<0>(a, tab, stream);
     }
-}
-
-extern "C" void afxk_mel2_destroy(void *plan) {
-    Plan2 *p = static_cast<Plan2 *>(plan);
-    if (!p) return;
-    afxdev_free(p->dTab);
-    afxdev_free(p->dMeta);
-    free(p);
-}
-
-// variant: index into {48+16, 72+32} taps (afxk_melfused_variant for radix2Exp 11)
-extern "C" int afxk_mel2_create(void **plan, int variant, const float *hWindow, const AfxBandPlan *band, void *stream) {
-    *plan = nullptr;
-    if (variant < 0 || variant > 1) return AFX_ERR_UNSUPPORTED;
-    const int TA = kVariants[variant].tapsA, TB = kVariants[variant].tapsB;
-    const int WP = wpitch(TA, TB);
-    const size_t bytes = (size_t)tab_bytes(TA, TB);
-    Plan2 *p = static_cast<Plan2 *>(calloc(1, sizeof(Plan2)));
-    float *tab = static_cast<float *>(calloc(bytes, 1));
-    if (!p || !tab) {
-        free(p);
-        free(tab);
-        return AFX_ERR_NOMEM;
-    }
-    p->variant = variant;
-    p->num = band->num;
-    p->split = band->split;
-    fill_tables(tab, hWindow);
-    float *wL = tab + T_BAND / 4;
-    for (int l = 0; l < 64; ++l) {
-        for (int t = 0; t < band->tapsA; ++t) wL[(size_t)l * WP + t] = band->wA[(size_t)t * 64 + l];
-        for (int t = 0; t < band->tapsB; ++t) wL[(size_t)l * WP + TA + t] = band->wB[(size_t)t * 64 + l];
-    }
-    int meta[384];
-    for (int l = 0; l < 64; ++l) {
-        meta[l] = band->startA[l];
-        meta[64 + l] = band->startB[l];
-        meta[128 + l] = band->rowA[l];
-        meta[192 + l] = band->rowB[l];
-        meta[256 + l] = (int)band->segIdx[l];
-        meta[320 + l] = (int)band->segIdx[64 + l];
-    }
-    int st = afxdev_malloc(reinterpret_cast<void **>(&p->dTab), bytes);
-    if (st == AFX_OK) st = afxdev_h2d(p->dTab, tab, bytes, stream);
-    if (st == AFX_OK) st = afxdev_malloc(reinterpret_cast<void **>(&p->dMeta), sizeof(meta));
-    if (st == AFX_OK) st = afxdev_h2d(p->dMeta, meta, sizeof(meta), stream);
-    if (st == AFX_OK) st = afxdev_stream_sync(stream);  // host staging buffers are freed below
-    free(tab);
-    if (st != AFX_OK) {
-        afxk_mel2_destroy(p);
-        return st;
-    }
-    *plan = p;
-    return AFX_OK;
-}
-
-// specMap 0 / 1 / 2: real results, 3 / 4: complex results (out + outIm); AFX_ERR_UNSUPPORTED when the requested fusion
-// (cepstra / temporal features) does not apply to this plan
-extern "C" int afxk_mel2_run(void *plan, const AfxMelFusedArgs *a, void *stream) {
-    const Plan2 *p = static_cast<const Plan2 *>(plan);
-    if (!p || a->specMap > 4) return AFX_ERR_ARG;
-    return p->variant == 0 ? launch<48, 16>(p, a, stream) : launch<72, 32>(p, a, stream);
 }

@@ -23,22 +23,16 @@
 // (spectrum value, bank product).
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 
-#include "afx_device.h"
-#include "afx_hipcheck.h"
-#include "afx_pkmath.h"
+#include "afx_melplan.h"
+#include "afx_melparts.h"
 #include "afx_ccblock.h"
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int NFFT = 4096;
 constexpr int MC = 1024;                     // complex length of one half
@@ -48,7 +42,7 @@ constexpr int PROW_OFF = 1024;               // byte offset of the power row in 
 constexpr int PROW_F = 2176;                 // 2049 bins + zero pad for the fixed-length band loops (afx_bft_fast.c: v4k)
 constexpr int WAVE_LDS = PROW_OFF + PROW_F * 4;  // 9728: the pad [9220, 9728) lies behind both images
 static_assert(16 * P1 * 8 <= PROW_OFF + 2049 * 4, "exchange image must end before the zero pad");
-// table blob, byte offsets (built on the host by afxk_mel4k2_create, copied to LDS per workgroup)
+// table blob, byte offsets (built on the host by fill_transform_tables + afxk_melfused_create, copied to LDS per workgroup)
 constexpr int T_WIN = 0;                     // [2 halves][8][64] float4: (w[4m+2h], w[4m+2h+1]) of rows n1 = 2j, 2j + 1
 constexpr int T_TW1 = 16384;                 // [8][64] float4: W_1024^(lane k1), k1 = 2j, 2j + 1
 constexpr int T_TW2 = 24576;                 // [4] rows of 16 float2, TW2_PITCH bytes apart: W_64^(m2 j1)
@@ -85,12 +79,6 @@ struct KArgs4 {
     float *cc;             // [totalFrames, ccNum]
 };
 
-// orders this wave's LDS stores before its later LDS loads of other lanes' data (afx_melfused2.hip)
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-}
-
 // wave priority by phase of the frame, as in afx_melfused2.hip (transform phases above window / band / store)
 #ifndef AFX_PRIO4K_MASK
 #define AFX_PRIO4K_MASK 0x1E
@@ -100,20 +88,8 @@ __device__ __forceinline__ void wave_lds_sync() {
         if (AFX_PRIO4K_MASK != 0) __builtin_amdgcn_s_setprio(((AFX_PRIO4K_MASK >> (p)) & 1) ? 1 : 0); \
     } while (0)
 
-__device__ __forceinline__ v2 lo2(v4f q) { return v2{q.x, q.y}; }
-__device__ __forceinline__ v2 hi2(v4f q) { return v2{q.z, q.w}; }
-
-// |X|^2 of the conjugate pair (a, 2048-a) from A = Z[a], B = Z[2048-a], w = 0.5 W_4096^a
-__device__ __forceinline__ void split_pair(v2 A, v2 B, v2 w, float &pa, float &pb) {
-    const v2 e2 = pk_add_conj(A, B);   // 2 E
-    const v2 d = pk_sub_conj(A, B);    // 2 i O
-    const v2 wo = cmul_mi(d, w);       // W O
-    const v2 x = e2 * 0.5f + wo;       // X[a]
-    const v2 y = e2 * 0.5f - wo;       // conj(X[2048-a])
-    pa = x.x * x.x + x.y * x.y;
-    pb = y.x * y.x + y.y * y.y;
-}
-// the same for the pair (1024-k, 1024+k): A = Z[1024-k], B = Z[1024+k], its twiddle is -i conj(w), w = 0.5 W_4096^k
+// (wave_lds_sync, lo2 / hi2, split_pair, split_pair_c, cplx_map: afx_melparts.h; stft_map: afx_pkmath.h)
+// split_pair for the pair (1024-k, 1024+k): A = Z[1024-k], B = Z[1024+k], its twiddle is -i conj(w), w = 0.5 W_4096^k
 __device__ __forceinline__ void split_pair_q(v2 A, v2 B, v2 w, float &pa, float &pb) {
     const v2 e2 = pk_add_conj(A, B);
     const v2 d = pk_sub_conj(A, B);
@@ -124,14 +100,7 @@ __device__ __forceinline__ void split_pair_q(v2 A, v2 B, v2 w, float &pa, float 
     pb = y.x * y.x + y.y * y.y;
 }
 
-// complex results: the spectrum values themselves (x = X[a], y = conj(X[2048-a]); q variant: x = X[1024-k], y = conj(X[1024+k]))
-__device__ __forceinline__ void split_pair_c(v2 A, v2 B, v2 w, v2 &x, v2 &y) {
-    const v2 e2 = pk_add_conj(A, B);
-    const v2 d = pk_sub_conj(A, B);
-    const v2 wo = cmul_mi(d, w);
-    x = e2 * 0.5f + wo;
-    y = e2 * 0.5f - wo;
-}
+// complex results, q variant: x = X[1024-k], y = conj(X[1024+k])
 __device__ __forceinline__ void split_pair_qc(v2 A, v2 B, v2 w, v2 &x, v2 &y) {
     const v2 e2 = pk_add_conj(A, B);
     const v2 d = pk_sub_conj(A, B);
@@ -139,26 +108,6 @@ __device__ __forceinline__ void split_pair_qc(v2 A, v2 B, v2 w, v2 &x, v2 &y) {
     x = e2 * 0.5f - vv;
     y = e2 * 0.5f + vv;
 }
-// (re, im) of the requested complex result from a spectrum value c: S (sq = false) or S^2 (bft_algorithm.c:457-485)
-__device__ __forceinline__ void cplx_map(v2 c, bool sq, float &re, float &im) {
-    re = sq ? c.x * c.x - c.y * c.y : c.x;
-    im = sq ? 2.f * (c.x * c.y) : c.y;
-}
-
-// what an STFT instantiation stores for a spectrum value (the maps of afx_stft.hip)
-__device__ __forceinline__ void stft_map(float re, float im, int mode, float normValue, float &v0, float &v1) {
-    v1 = 0.f;
-    switch (mode) {
-        case AFX_SPEC_COMPLEX: v0 = re; v1 = im; break;
-        case AFX_SPEC_POWER: v0 = re * re + im * im; break;
-        case AFX_SPEC_MAG: v0 = sqrtf(re * re + im * im); break;
-        case AFX_SPEC_SQUARE: v0 = re * re - im * im; v1 = 2.f * re * im; break;
-        case AFX_SPEC_MAG_NORM: v0 = powf(sqrtf(re * re + im * im), normValue); break;
-        case AFX_SPEC_PHASE: v0 = atan2f(im, re < 1e-16f ? 1e-16f : re); break;
-        default: v0 = powf(re * re + im * im, normValue); break;  // AFX_SPEC_POWER_NORM
-    }
-}
-
 // SHIFT: hop = 256 * SHIFT samples -> the next frame's register image is this one moved down by SHIFT float4,
 //   only SHIFT new float4 per lane are fetched (0: every frame fetched whole)
 // SPLIT: the plan's slots hold row SEGMENTS (afx_bandplan_build_split)
@@ -184,7 +133,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void k_stft_band_4k2(KArgs4 a) {
         float4 *s4 = reinterpret_cast<float4 *>(smem);
         for (int i = threadIdx.x + (STFT ? T_TW1 / 16 : 0); i < TABB / 16; i += WAVES * 64) s4[i] = a.tab[i];
         if constexpr (STFT) {
-            // the window of each half in pair layout from the object's natural-order window (afxk_mel4k_create builds the same)
+            // the window of each half in pair layout from the object's natural-order window (fill_transform_tables builds the same)
             v2 *winT = reinterpret_cast<v2 *>(smem + T_WIN);
             for (int i = threadIdx.x; i < 2048; i += WAVES * 64) {
                 const int h = i >> 10, n1 = (i >> 6) & 15, l = i & 63;
@@ -571,52 +520,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void k_stft_band_4k2(KArgs4 a) {
         //         ds_read_b64; the NEXT block of four quads is requested before this block's values are waited for ----
         float accA, accB;
         {
-            constexpr int QA = TA / 4, QB = TB / 4, QT = QA + QB, BLK = 4, NB = (QT + BLK - 1) / BLK;
-            v2 sA = {0.f, 0.f}, sB = {0.f, 0.f};
-            v4f w[2][BLK];
-            v2 p0[2][BLK], p1[2][BLK];
-            auto request = [&](int blk, v4f (&wq)[BLK], v2 (&q0v)[BLK], v2 (&q1v)[BLK]) {
-#pragma unroll
-                for (int i = 0; i < BLK; ++i) {
-                    const int q = blk * BLK + i;
-                    if (q >= QT) continue;
-                    RD128(wq[i], awr, 16 * q);
-                    if (q < QA) {
-                        RD64(q0v[i], apa, 16 * q);
-                        RD64(q1v[i], apa, 16 * q + 8);
-                    } else {
-                        RD64(q0v[i], apb, 16 * (q - QA));
-                        RD64(q1v[i], apb, 16 * (q - QA) + 8);
-                    }
-                }
-            };
-            request(0, w[0], p0[0], p1[0]);
-#pragma unroll
-            for (int blk = 0; blk < NB; ++blk) {
-                const int cur = blk & 1;
-                const int nextQuads = (blk + 1 < NB) ? ((QT - (blk + 1) * BLK) < BLK ? (QT - (blk + 1) * BLK) : BLK) : 0;
-                if (blk + 1 < NB) request(blk + 1, w[cur ^ 1], p0[cur ^ 1], p1[cur ^ 1]);
-                if (nextQuads == 4) LDS_WAIT_N(12);
-                else if (nextQuads == 3) LDS_WAIT_N(9);
-                else if (nextQuads == 2) LDS_WAIT_N(6);
-                else if (nextQuads == 1) LDS_WAIT_N(3);
-                else LDS_WAIT_N(0);
-#pragma unroll
-                for (int i = 0; i < BLK; ++i) {
-                    if (blk * BLK + i >= QT) continue;
-                    PIN(w[cur][i]);
-                    PIN(p0[cur][i]);
-                    PIN(p1[cur][i]);
-                    const int q = blk * BLK + i;
-                    if (q < QA) {
-                        sA += lo2(w[cur][i]) * p0[cur][i];
-                        sA += hi2(w[cur][i]) * p1[cur][i];
-                    } else {
-                        sB += lo2(w[cur][i]) * p0[cur][i];
-                        sB += hi2(w[cur][i]) * p1[cur][i];
-                    }
-                }
-            }
+            v2 sA, sB;
+            band_stage<TA, TB, 4, false>(awr, apa, apb, sA, sB);
             accA = hsum(sA);
             accB = hsum(sB);
         }
@@ -723,45 +628,14 @@ void fill_transform_tables(float *tab, const float *hWindow) {
             }
 }
 
-// the STFT instantiations' twiddle blob (bytes [T_TW1, tab_bytes(0, 0)) are read), one device copy per device, never freed
-const float4 *stft_tables(void *stream) {
-    static std::mutex mu;
-    static float4 *dTab[AFX_MAX_DEVICES] = {};
-    const int dev = afxdev_current_device();
-    if (dev < 0 || dev >= AFX_MAX_DEVICES) return nullptr;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!dTab[dev]) {
-        const size_t bytes = (size_t)tab_bytes(0, 0);
-        float *h = static_cast<float *>(calloc(bytes, 1));
-        float4 *d = nullptr;
-        if (!h) return nullptr;
-        fill_transform_tables(h, nullptr);
-        int st = afxdev_malloc(reinterpret_cast<void **>(&d), bytes);
-        // (a synchronous copy, like wave_tables() of afx_stft.hip: the caller's stream is not waited for under this lock)
-        if (st == AFX_OK && hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) != hipSuccess) st = AFX_ERR_HIP;
-        free(h);
-        if (st != AFX_OK) {
-            afxdev_free(d);
-            return nullptr;
-        }
-        dTab[dev] = d;
-    }
-    return dTab[dev];
-}
+// the STFT instantiations' twiddle blob (bytes [T_TW1, tab_bytes(0, 0)) are read; afx_device_table)
+void fill_stft_tables(float *tab) { fill_transform_tables(tab, nullptr); }
 
 template <int SHIFT, bool MAPPED, bool FULL>
-int launch_stft(const AfxStftArgs *a, const float4 *tab, void *stream) {
+int launch_stft(const AfxStftArgs *a, const float *tab, void *stream) {
     const long long total = (long long)a->batch * a->timeLength;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    long long waves = (long long)cus * WAVES * 2;
-    long long fpw = (total + waves - 1) / waves;
-    if (fpw < 16) {  // (launch_variant: a call that cannot fill one round of workgroups is spread over all CUs)
-        const long long oneRound = (total + (long long)cus * WAVES - 1) / ((long long)cus * WAVES);
-        fpw = oneRound < 16 ? oneRound : 16;
-    }
-    const long long usedWaves = (total + fpw - 1) / fpw;
-    const long long blocks = (usedWaves + WAVES - 1) / WAVES;
+    long long fpw;
+    const long long blocks = afx_mel_frames(total, WAVES, &fpw);
     KArgs4 k;
     memset(&k, 0, sizeof(k));
     k.x = a->x;
@@ -770,7 +644,7 @@ int launch_stft(const AfxStftArgs *a, const float4 *tab, void *stream) {
     k.timeLength = a->timeLength;
     k.hop = a->hop;
     k.framesPerWave = (int)fpw;
-    k.tab = tab;
+    k.tab = reinterpret_cast<const float4 *>(tab);
     k.specMap = 3;
     k.normValue = a->normValue;
     k.out = a->outRe;
@@ -781,49 +655,21 @@ int launch_stft(const AfxStftArgs *a, const float4 *tab, void *stream) {
     k.binCount = a->binCount;
     k.outPitch = a->outPitch ? a->outPitch : (long long)a->binCount;
     constexpr size_t lds = (size_t)block_lds_bytes(0, 0);
-    static std::atomic<bool> attrSet[AFX_MAX_DEVICES];
-    const int attrDev = afxdev_current_device() & (AFX_MAX_DEVICES - 1);
-    if (!attrSet[attrDev].load(std::memory_order_acquire)) {  // (two threads may both set it: idempotent)
-        AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_stft_band_4k2<0, 0, SHIFT, false, true, true, MAPPED, FULL>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attrSet[attrDev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((k_stft_band_4k2<0, 0, SHIFT, false, true, true, MAPPED, FULL>), dim3((unsigned)blocks), dim3(WAVES * 64), lds,
-                       (hipStream_t)stream, k);
+    AFX_LAUNCH_DYN_LDS((k_stft_band_4k2<0, 0, SHIFT, false, true, true, MAPPED, FULL>), dim3((unsigned)blocks), dim3(WAVES * 64), lds, stream, k);
     AFX_LAUNCH_CHECK("k_stft_band_4k2<stft>");
     return AFX_OK;
 }
 
-struct Plan4 {
-    int variant;  // 200 + index into kVariants: FIRST field (afx_melfused.hip: variant >= 200 -> this file)
-    int num, split;
-    float4 *dTab;
-    int *dMeta;
-};
-struct Variant {
-    int tapsA, tapsB;
-};
-constexpr Variant kVariants[] = {{96, 32}, {128, 64}, {176, 8}};
+constexpr AfxMelVariant kVariants[] = {{96, 32}, {128, 64}, {176, 8}};
 static_assert(block_lds_bytes(96, 32) <= 163840 && block_lds_bytes(128, 64) <= 163840 && block_lds_bytes(176, 8) <= 163840,
               "tables + weights + 8 wave regions must fit the 160 KB LDS");
 
 template <int TA, int TB, int SHIFT, bool SPLIT, bool CPLX, bool CC = false>
-int launch_variant(const Plan4 *p, const AfxMelFusedArgs *a, void *stream) {
+int launch_variant(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
     const long long total = (long long)a->batch * a->timeLength;
     if (total <= 0) return AFX_OK;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    long long waves = (long long)cus * WAVES * 2;  // two rounds of workgroups (afx_melfused2.hip)
-    long long fpw = (total + waves - 1) / waves;
-    // long runs per wave (register re-use of the overlapping frames) once a round of workgroups is full; a call that
-    // cannot fill one round -- the one-clip legacy entry points: 1000 frames -- is spread over all CUs instead
-    // (16 frames in sequence per wave were 75 us of a 1000-frame call's 190, profiles/r05_legacy_phases.txt)
-    if (fpw < 16) {
-        const long long oneRound = (total + (long long)cus * WAVES - 1) / ((long long)cus * WAVES);
-        fpw = oneRound < 16 ? oneRound : 16;
-    }
-    const long long usedWaves = (total + fpw - 1) / fpw;
-    const long long blocks = (usedWaves + WAVES - 1) / WAVES;
+    long long fpw;
+    const long long blocks = afx_mel_frames(total, WAVES, &fpw);
 
     KArgs4 k;
     memset(&k, 0, sizeof(k));
@@ -834,7 +680,7 @@ int launch_variant(const Plan4 *p, const AfxMelFusedArgs *a, void *stream) {
     k.hop = a->hop;
     k.framesPerWave = (int)fpw;
     k.aligned = ((a->clipStride & 3) == 0) && ((a->hop & 3) == 0) && ((reinterpret_cast<uintptr_t>(a->x) & 15) == 0);
-    k.tab = p->dTab;
+    k.tab = reinterpret_cast<const float4 *>(p->dTab);
     k.meta = p->dMeta;
     k.specMap = a->specMap;
     k.postPow = a->postPow;
@@ -847,21 +693,13 @@ int launch_variant(const Plan4 *p, const AfxMelFusedArgs *a, void *stream) {
     k.ccCbrt = a->ccRectify == 1;
     k.cc = a->cc;
     constexpr size_t lds = (size_t)block_lds_bytes(TA, TB);
-    static std::atomic<bool> attrSet[AFX_MAX_DEVICES];  // per device: the attribute lives in the device's code object
-    const int attrDev = afxdev_current_device() & (AFX_MAX_DEVICES - 1);
-    if (!attrSet[attrDev].load(std::memory_order_acquire)) {  // (two threads may both set it: idempotent)
-        AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_stft_band_4k2<TA, TB, SHIFT, SPLIT, CPLX, false, false, false, CC>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attrSet[attrDev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((k_stft_band_4k2<TA, TB, SHIFT, SPLIT, CPLX, false, false, false, CC>), dim3((unsigned)blocks), dim3(WAVES * 64), lds,
-                       (hipStream_t)stream, k);
+    AFX_LAUNCH_DYN_LDS((k_stft_band_4k2<TA, TB, SHIFT, SPLIT, CPLX, false, false, false, CC>), dim3((unsigned)blocks), dim3(WAVES * 64), lds, stream, k);
     AFX_LAUNCH_CHECK("k_stft_band_4k2");
     return AFX_OK;
 }
 
 template <int TA, int TB, bool CPLX>
-int launch_mode(const Plan4 *p, const AfxMelFusedArgs *a, void *stream) {
+int launch_mode(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
     // register re-use of the overlapping frames at the wrapper's default hop = N/4; other hops fetch every frame whole
     if (a->hop == 1024)
         return p->split ? launch_variant<TA, TB, 4, true, CPLX>(p, a, stream) : launch_variant<TA, TB, 4, false, CPLX>(p, a, stream);
@@ -869,7 +707,7 @@ int launch_mode(const Plan4 *p, const AfxMelFusedArgs *a, void *stream) {
 }
 
 template <int TA, int TB>
-int launch(const Plan4 *p, const AfxMelFusedArgs *a, void *stream) {
+int launch(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
     if (a->specMap >= 3) {  // complex results: S (3) or S^2 (4)
         if (a->cc) return AFX_ERR_UNSUPPORTED;
         if (!a->outIm) return AFX_ERR_ARG;
@@ -885,85 +723,21 @@ int launch(const Plan4 *p, const AfxMelFusedArgs *a, void *stream) {
     return launch_mode<TA, TB, false>(p, a, stream);
 }
 
-}  // namespace
-
-// ---- the n_fft 4096 entry points of the fused dispatcher (afx_melfused.hip reads Plan4.variant >= 200 as "this file") ----
-extern "C" int afxk_mel4k_variant(int tapsA, int tapsB) {
-    for (int i = 0; i < 3; ++i)
-        if (tapsA <= kVariants[i].tapsA && tapsB <= kVariants[i].tapsB) return 200 + i;
-    return -1;
-}
-
-extern "C" int afxk_mel4k_kind(const void *plan) {
-    const Plan4 *p = static_cast<const Plan4 *>(plan);
-    return !p ? 0 : (p->split ? 202 : 201);
-}
-
-extern "C" void afxk_mel4k_destroy(void *plan) {
-    Plan4 *p = static_cast<Plan4 *>(plan);
-    if (!p) return;
-    afxdev_free(p->dTab);
-    afxdev_free(p->dMeta);
-    free(p);
-}
-
-extern "C" int afxk_mel4k_create(void **plan, const float *hWindow, const AfxBandPlan *band, void *stream) {
-    *plan = nullptr;
-    const int variant = afxk_mel4k_variant(band->tapsA, band->tapsB) - 200;  // index into {96+32, 128+64, 176+8} taps
-    if (variant < 0 || variant > 2) return AFX_ERR_UNSUPPORTED;
-    const int TA = kVariants[variant].tapsA, TB = kVariants[variant].tapsB;
-    const int WP = wpitch(TA, TB);
-    const size_t bytes = (size_t)tab_bytes(TA, TB);
-    Plan4 *p = static_cast<Plan4 *>(calloc(1, sizeof(Plan4)));
-    float *tab = static_cast<float *>(calloc(bytes, 1));
-    if (!p || !tab) {
-        free(p);
-        free(tab);
-        return AFX_ERR_NOMEM;
-    }
-    p->variant = 200 + variant;  // (first field: the dispatcher's tag)
-    p->num = band->num;
-    p->split = band->split;
-    fill_transform_tables(tab, hWindow);
-    float *wL = tab + T_BAND / 4;
-    for (int l = 0; l < 64; ++l) {
-        for (int t = 0; t < band->tapsA; ++t) wL[(size_t)l * WP + t] = band->wA[(size_t)t * 64 + l];
-        for (int t = 0; t < band->tapsB; ++t) wL[(size_t)l * WP + TA + t] = band->wB[(size_t)t * 64 + l];
-    }
-    int meta[384];
-    for (int l = 0; l < 64; ++l) {
-        meta[l] = band->startA[l];
-        meta[64 + l] = band->startB[l];
-        meta[128 + l] = band->rowA[l];
-        meta[192 + l] = band->rowB[l];
-        meta[256 + l] = (int)band->segIdx[l];
-        meta[320 + l] = (int)band->segIdx[64 + l];
-    }
-    int st = afxdev_malloc(reinterpret_cast<void **>(&p->dTab), bytes);
-    if (st == AFX_OK) st = afxdev_h2d(p->dTab, tab, bytes, stream);
-    if (st == AFX_OK) st = afxdev_malloc(reinterpret_cast<void **>(&p->dMeta), sizeof(meta));
-    if (st == AFX_OK) st = afxdev_h2d(p->dMeta, meta, sizeof(meta), stream);
-    if (st == AFX_OK) st = afxdev_stream_sync(stream);  // host staging buffers are freed below
-    free(tab);
-    if (st != AFX_OK) {
-        afxk_mel4k_destroy(p);
-        return st;
-    }
-    *plan = p;
-    return AFX_OK;
-}
-
 // specMap 0 / 1 / 2: real results; 3 / 4: complex results (out + outIm)
-extern "C" int afxk_mel4k_run(void *plan, const AfxMelFusedArgs *a, void *stream) {
-    if (a->energy) return AFX_ERR_UNSUPPORTED;  // temporal features ride along at n_fft 2048 only (cepstra: every size, launch())
-    const Plan4 *p = static_cast<const Plan4 *>(plan);
-    if (!p || a->specMap > 4) return AFX_ERR_ARG;
+int run(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
     switch (p->variant) {
-        case 200: return launch<96, 32>(p, a, stream);
-        case 201: return launch<128, 64>(p, a, stream);
-        case 202: return launch<176, 8>(p, a, stream);
+        case 0: return launch<96, 32>(p, a, stream);
+        case 1: return launch<128, 64>(p, a, stream);
+        case 2: return launch<176, 8>(p, a, stream);
         default: return AFX_ERR_UNSUPPORTED;
     }
+}
+
+}  // namespace
+
+const AfxMelSize *afx_mel_size4k() {
+    static const AfxMelSize size = {12, 200, kVariants, 3, T_BAND, fill_transform_tables, run};
+    return &size;
 }
 
 // n_fft 4096 without a bank (afxk_stft, afx_stft.hip): every frame inside its clip (no padding), no temporal features.
@@ -975,7 +749,7 @@ extern "C" int afxk_stft4k(const AfxStftArgs *a, void *stream) {
     const bool two = (a->mode == AFX_SPEC_COMPLEX || a->mode == AFX_SPEC_SQUARE);
     if (!a->outRe || (two && !a->outIm)) return AFX_ERR_ARG;
     if ((long long)a->batch * a->timeLength <= 0) return AFX_OK;
-    const float4 *tab = stft_tables(stream);
+    const float *tab = afx_device_table<fill_stft_tables>((size_t)tab_bytes(0, 0));
     if (!tab) return AFX_ERR_UNSUPPORTED;
     const bool s4 = a->hop == 1024;  // register re-use of the overlapping frames at the wrapper's default hop
     if (a->mode == AFX_SPEC_COMPLEX) {

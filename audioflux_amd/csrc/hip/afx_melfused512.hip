@@ -9,17 +9,13 @@
 // flux_complex.c:254-286,469-503, bft_algorithm.c:457-529, flux_vector.c:55-86).
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 
-#include "afx_device.h"
-#include "afx_hipcheck.h"
-#include "afx_pkmath.h"
+#include "afx_melplan.h"
+#include "afx_melparts.h"
 #include "afx_ccblock.h"
 
 #ifndef AFX_CC_GROUPS  // whole-row plans: 16-band groups of the rows requested per trip to the L2, and whether the next trip is requested ahead
@@ -28,10 +24,6 @@
 #endif
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ v2 lo2(v4f q) { return v2{q.x, q.y}; }
-__device__ __forceinline__ v2 hi2(v4f q) { return v2{q.z, q.w}; }
 
 constexpr int NFFT = 512;
 constexpr int MC = 256;            // complex FFT length
@@ -78,50 +70,6 @@ struct KArgs {
     int ccNum, ccCbrt;
     float *cc;             // [totalFrames, ccNum]
 };
-
-// what an STFT instantiation stores for a spectrum value (the maps of afx_stft.hip)
-__device__ __forceinline__ void stft_map(float re, float im, int mode, float normValue, float &v0, float &v1) {
-    v1 = 0.f;
-    switch (mode) {
-        case AFX_SPEC_COMPLEX: v0 = re; v1 = im; break;
-        case AFX_SPEC_POWER: v0 = re * re + im * im; break;
-        case AFX_SPEC_MAG: v0 = sqrtf(re * re + im * im); break;
-        case AFX_SPEC_SQUARE: v0 = re * re - im * im; v1 = 2.f * re * im; break;
-        case AFX_SPEC_MAG_NORM: v0 = powf(sqrtf(re * re + im * im), normValue); break;
-        case AFX_SPEC_PHASE: v0 = atan2f(im, re < 1e-16f ? 1e-16f : re); break;
-        default: v0 = powf(re * re + im * im, normValue); break;  // AFX_SPEC_POWER_NORM
-    }
-}
-
-// |X|^2 of the conjugate pair (k, 256-k) from A = Z[k], B = Z[256-k], w = 0.5 W_512^k
-__device__ __forceinline__ void split_pair(v2 A, v2 B, v2 w, float &pk, float &pq) {
-    const v2 e2 = pk_add_conj(A, B);
-    const v2 d = pk_sub_conj(A, B);
-    const v2 wo = cmul_mi(d, w);
-    const v2 x = e2 * 0.5f + wo;  // X[k]
-    const v2 y = e2 * 0.5f - wo;  // conj(X[256-k])
-    pk = x.x * x.x + x.y * x.y;
-    pq = y.x * y.x + y.y * y.y;
-}
-__device__ __forceinline__ void split_pair_c(v2 A, v2 B, v2 w, bool sq, float &kr, float &ki, float &qr,
-                                             float &qi) {
-    const v2 e2 = pk_add_conj(A, B);
-    const v2 d = pk_sub_conj(A, B);
-    const v2 wo = cmul_mi(d, w);
-    const v2 x = e2 * 0.5f + wo;
-    const v2 y = e2 * 0.5f - wo;
-    if (sq) {
-        kr = x.x * x.x - x.y * x.y;
-        ki = 2.f * (x.x * x.y);
-        qr = y.x * y.x - y.y * y.y;
-        qi = -2.f * (y.x * y.y);
-    } else {
-        kr = x.x;
-        ki = x.y;
-        qr = y.x;
-        qi = -y.y;
-    }
-}
 
 // GENERAL: magnitude / norm exponent / post power (real results); SHIFT: hop = 128 SHIFT samples = SHIFT registers;
 // CPLX: complex results (specMap 3: S, 4: S^2), the bank runs over the real and the imaginary parts in turn
@@ -332,10 +280,10 @@ __global__ __launch_bounds__(WAVES * 64) void k_stft_band_512(KArgs a) {
             PIN(zb[0]); PIN(zb[1]); PIN(ws[0]); PIN(ws[1]); PIN(zm); PIN(wm);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                if (CPLX) split_pair_c(v[j], zb[j], ws[j], !STFT && a.specMap == 4, pk[j], pkI[CPLX ? j : 0], pq[j], pqI[CPLX ? j : 0]);
+                if (CPLX) split_pair_cmap(v[j], zb[j], ws[j], !STFT && a.specMap == 4, pk[j], pkI[CPLX ? j : 0], pq[j], pqI[CPLX ? j : 0]);
                 else split_pair(v[j], zb[j], ws[j], pk[j], pq[j]);
             }
-            if (CPLX) split_pair_c(zm, zm, wm, !STFT && a.specMap == 4, pk[2], pkI[CPLX ? 2 : 0], pq[2], pqI[CPLX ? 2 : 0]);
+            if (CPLX) split_pair_cmap(zm, zm, wm, !STFT && a.specMap == 4, pk[2], pkI[CPLX ? 2 : 0], pq[2], pqI[CPLX ? 2 : 0]);
             else split_pair(zm, zm, wm, pk[2], pq[2]);
         }
         if (CPLX) {
@@ -405,53 +353,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_stft_band_512(KArgs a) {
             // ---- 4. banded filter bank (afx_melfused1k.hip) ----
             float accA, accB;
             {
-                constexpr int QA = TA / 4, QB = TB / 4, QT = QA + QB, BLK = 4, NB = (QT + BLK - 1) / BLK;
-                v2 sA = {0.f, 0.f}, sB = {0.f, 0.f};
-                v4f w[2][BLK];
-                v2 p0[2][BLK], p1[2][BLK];
-                auto request = [&](int blk, v4f (&wq)[BLK], v2 (&q0v)[BLK], v2 (&q1v)[BLK]) {
-#pragma unroll
-                    for (int i = 0; i < BLK; ++i) {
-                        const int q = blk * BLK + i;
-                        if (q >= QT) continue;
-                        RD128(wq[i], awr, 16 * q);
-                        if (q < QA) {
-                            RD64(q0v[i], apa, 16 * q);
-                            RD64(q1v[i], apa, 16 * q + 8);
-                        } else {
-                            RD64(q0v[i], apb, 16 * (q - QA));
-                            RD64(q1v[i], apb, 16 * (q - QA) + 8);
-                        }
-                    }
-                };
-                request(0, w[0], p0[0], p1[0]);
-#pragma unroll
-                for (int blk = 0; blk < NB; ++blk) {
-                    const int cur = blk & 1;
-                    const int nextQuads = (blk + 1 < NB) ? ((QT - (blk + 1) * BLK) < BLK ? (QT - (blk + 1) * BLK) : BLK) : 0;
-                    if (blk + 1 < NB) request(blk + 1, w[cur ^ 1], p0[cur ^ 1], p1[cur ^ 1]);
-                    if (nextQuads == 4) LDS_WAIT_N(12);
-                    else if (nextQuads == 3) LDS_WAIT_N(9);
-                    else if (nextQuads == 2) LDS_WAIT_N(6);
-                    else if (nextQuads == 1) LDS_WAIT_N(3);
-                    else LDS_WAIT_N(0);
-#pragma unroll
-                    for (int i = 0; i < BLK; ++i) {
-                        if (blk * BLK + i >= QT) continue;
-                        PIN(w[cur][i]);
-                        PIN(p0[cur][i]);
-                        PIN(p1[cur][i]);
-                        if (blk * BLK + i < QA) {
-                            sA += lo2(w[cur][i]) * p0[cur][i];
-                            sA += hi2(w[cur][i]) * p1[cur][i];
-                        } else {
-                            sB += lo2(w[cur][i]) * p0[cur][i];
-                            sB += hi2(w[cur][i]) * p1[cur][i];
-                        }
-                    }
-                    PIN(sA);  // (this block's sums before the next block's requests: afx_melfused1k.hip)
-                    PIN(sB);
-                }
+                v2 sA, sB;
+                band_stage<TA, TB, 4, true>(awr, apa, apb, sA, sB);
                 accA = sA.x + sA.y;
                 accB = sB.x + sB.y;
             }
@@ -527,33 +430,15 @@ void fill_transform_tables(float *tab, const float *hWindow) {
     for (int k = 0; k <= 128; ++k) put(T_TWS, k, -2.0 * PI * (double)k / NFFT, 0.5);
 }
 
-struct Plan {
-    int variant;  // >= 300: this file (afxk_melfused_* dispatches on it)
-    int num, split;
-    float *dTab;
-    int *dMeta;
-};
-struct Variant {
-    int tapsA, tapsB;
-};
 // 257 bins: mel-128 needs 12-15 + 3 taps, mel-80 17-24, mel-64 20-28, mel-40 27-45, mel-26 41-61 (8 .. 44.1 kHz)
-constexpr Variant kVariants[] = {{16, 4}, {32, 4}, {48, 4}, {64, 8}};
-constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
+constexpr AfxMelVariant kVariants[] = {{16, 4}, {32, 4}, {48, 4}, {64, 8}};
 
 template <int TA, int TB, bool GENERAL, int SHIFT, bool CPLX, bool SPLIT = false, bool CC = false>
-int launch_variant(const Plan *p, const AfxMelFusedArgs *a, void *stream) {
+int launch_variant(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
     const long long total = (long long)a->batch * a->timeLength;
     if (total <= 0) return AFX_OK;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    long long waves = (long long)cus * WAVES * 2;
-    long long fpw = (total + waves - 1) / waves;
-    if (fpw < 16) {  // (afx_melfused1k.hip: a call that cannot fill one round of workgroups is spread over all CUs)
-        const long long oneRound = (total + (long long)cus * WAVES - 1) / ((long long)cus * WAVES);
-        fpw = oneRound < 16 ? oneRound : 16;
-    }
-    const long long usedWaves = (total + fpw - 1) / fpw;
-    const long long blocks = (usedWaves + WAVES - 1) / WAVES;
+    long long fpw;
+    const long long blocks = afx_mel_frames(total, WAVES, &fpw);
     KArgs k;
     k.x = a->x;
     k.clipStride = a->clipStride;
@@ -576,21 +461,13 @@ int launch_variant(const Plan *p, const AfxMelFusedArgs *a, void *stream) {
     k.cc = a->cc;
     constexpr size_t lds = (size_t)block_lds_bytes(TA, TB) + (CC ? CCB_BYTES : 0);  // (CC: the DCT operand table behind the wave regions)
     static_assert(lds <= 163840, "workgroup LDS budget");
-    static std::atomic<bool> attrSet[AFX_MAX_DEVICES];  // per device: the attribute lives in the device's code object
-    const int attrDev = afxdev_current_device() & (AFX_MAX_DEVICES - 1);
-    if (!attrSet[attrDev].load(std::memory_order_acquire)) {  // (two threads may both set it: idempotent)
-        AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_stft_band_512<TA, TB, GENERAL, SHIFT, CPLX, false, false, false, SPLIT, CC>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attrSet[attrDev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((k_stft_band_512<TA, TB, GENERAL, SHIFT, CPLX, false, false, false, SPLIT, CC>), dim3((unsigned)blocks), dim3(WAVES * 64), lds,
-                       (hipStream_t)stream, k);
+    AFX_LAUNCH_DYN_LDS((k_stft_band_512<TA, TB, GENERAL, SHIFT, CPLX, false, false, false, SPLIT, CC>), dim3((unsigned)blocks), dim3(WAVES * 64), lds, stream, k);
     AFX_LAUNCH_CHECK("k_stft_band_512");
     return AFX_OK;
 }
 
 template <int TA, int TB>
-int launch(const Plan *p, const AfxMelFusedArgs *a, void *stream) {
+int launch(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
     const bool general = (a->specMap != 0) || a->postPow;
     const bool shift1 = (a->hop == 128);  // hop = 128 * SHIFT
     if (a->cc) {  // cepstra in the same launch: real results, plain power rows on whole-row plans, every real mode on split plans
@@ -621,124 +498,33 @@ int launch(const Plan *p, const AfxMelFusedArgs *a, void *stream) {
                   : launch_variant<TA, TB, false, 0, false>(p, a, stream);
 }
 
-}  // namespace
-
-extern "C" int afxk_mel512_variant(int tapsA, int tapsB) {
-    for (int i = 0; i < kNumVariants; ++i)
-        if (tapsA <= kVariants[i].tapsA && tapsB <= kVariants[i].tapsB) return 300 + i;
-    return -1;
-}
-
-extern "C" int afxk_mel512_kind(const void *plan) {
-    const Plan *p = static_cast<const Plan *>(plan);
-    return !p ? 0 : (p->split ? 302 : 301);
-}
-
-extern "C" void afxk_mel512_destroy(void *plan) {
-    Plan *p = static_cast<Plan *>(plan);
-    if (!p) return;
-    afxdev_free(p->dTab);
-    afxdev_free(p->dMeta);
-    free(p);
-}
-
-extern "C" int afxk_mel512_create(void **plan, const float *hWindow, const AfxBandPlan *band, void *stream) {
-    *plan = nullptr;
-    const int variant = afxk_mel512_variant(band->tapsA, band->tapsB);
-    if (variant < 0) return AFX_ERR_UNSUPPORTED;
-    const int TA = kVariants[variant - 300].tapsA, TB = kVariants[variant - 300].tapsB;
-    const int WP = wpitch(TA, TB);
-    const size_t bytes = (size_t)TAB_BYTES + (size_t)64 * WP * 4;
-    Plan *p = static_cast<Plan *>(calloc(1, sizeof(Plan)));
-    float *tab = static_cast<float *>(calloc(bytes, 1));
-    if (!p || !tab) {
-        free(p);
-        free(tab);
-        return AFX_ERR_NOMEM;
-    }
-    p->variant = variant;
-    p->num = band->num;
-    p->split = band->split;
-    fill_transform_tables(tab, hWindow);
-    float *wL = tab + TAB_BYTES / 4;
-    int meta[384];  // startA | startB | rowA | rowB | segIdx[0..63] | segIdx[64..127]
-    for (int l = 0; l < 64; ++l) {
-        for (int t = 0; t < band->tapsA; ++t) wL[(size_t)l * WP + t] = band->wA[(size_t)t * 64 + l];
-        for (int t = 0; t < band->tapsB; ++t) wL[(size_t)l * WP + TA + t] = band->wB[(size_t)t * 64 + l];
-        meta[l] = band->startA[l];
-        meta[64 + l] = band->startB[l];
-        meta[128 + l] = band->rowA[l];
-        meta[192 + l] = band->rowB[l];
-        meta[256 + l] = (int)band->segIdx[l];
-        meta[320 + l] = (int)band->segIdx[64 + l];
-    }
-    int st = afxdev_malloc(reinterpret_cast<void **>(&p->dTab), bytes);
-    if (st == AFX_OK) st = afxdev_h2d(p->dTab, tab, bytes, stream);
-    if (st == AFX_OK) st = afxdev_malloc(reinterpret_cast<void **>(&p->dMeta), sizeof(meta));
-    if (st == AFX_OK) st = afxdev_h2d(p->dMeta, meta, sizeof(meta), stream);
-    if (st == AFX_OK) st = afxdev_stream_sync(stream);  // host staging buffers are freed below
-    free(tab);
-    if (st != AFX_OK) {
-        afxk_mel512_destroy(p);
-        return st;
-    }
-    *plan = p;
-    return AFX_OK;
-}
-
-extern "C" int afxk_mel512_run(void *plan, const AfxMelFusedArgs *a, void *stream) {
-    if (a->energy) return AFX_ERR_UNSUPPORTED;  // temporal features ride along at n_fft 2048 only (cepstra: every size, launch())
-    const Plan *p = static_cast<const Plan *>(plan);
-    if (!p || a->specMap > 4) return AFX_ERR_ARG;
+int run(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
     switch (p->variant) {
-        case 300: return launch<16, 4>(p, a, stream);
-        case 301: return launch<32, 4>(p, a, stream);
-        case 302: return launch<48, 4>(p, a, stream);
-        case 303: return launch<64, 8>(p, a, stream);
+        case 0: return launch<16, 4>(p, a, stream);
+        case 1: return launch<32, 4>(p, a, stream);
+        case 2: return launch<48, 4>(p, a, stream);
+        case 3: return launch<64, 8>(p, a, stream);
         default: return AFX_ERR_UNSUPPORTED;
     }
+}
+
+}  // namespace
+
+const AfxMelSize *afx_mel_size512() {
+    static const AfxMelSize size = {9, 300, kVariants, 4, TAB_BYTES, fill_transform_tables, run};
+    return &size;
 }
 
 // ---- n_fft 512 without a bank (afxk_stft, afx_stft.hip): every frame inside its clip (no padding), no temporal features.
 namespace {
 
-const float *stft_tables(void *stream) {  // one device copy of the twiddle blob per device, never freed
-    static std::mutex mu;
-    static float *dTab[AFX_MAX_DEVICES] = {};
-    const int dev = afxdev_current_device();
-    if (dev < 0 || dev >= AFX_MAX_DEVICES) return nullptr;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!dTab[dev]) {
-        float *h = static_cast<float *>(calloc(TAB_BYTES, 1));
-        if (!h) return nullptr;
-        fill_transform_tables(h, nullptr);
-        float *d = nullptr;
-        int st = afxdev_malloc(reinterpret_cast<void **>(&d), TAB_BYTES);
-        // (a synchronous copy, like wave_tables() of afx_stft.hip: the caller's stream is not waited for under this lock)
-        if (st == AFX_OK && hipMemcpy(d, h, TAB_BYTES, hipMemcpyHostToDevice) != hipSuccess) st = AFX_ERR_HIP;
-        free(h);
-        if (st != AFX_OK) {
-            afxdev_free(d);
-            return nullptr;
-        }
-        dTab[dev] = d;
-    }
-    return dTab[dev];
-}
+void fill_stft_tables(float *tab) { fill_transform_tables(tab, nullptr); }  // the twiddle blob of the STFT instantiations (afx_device_table)
 
 template <int SHIFT, bool MAPPED, bool FULL>
 int launch_stft(const AfxStftArgs *a, const float *tab, void *stream) {
     const long long total = (long long)a->batch * a->timeLength;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    long long waves = (long long)cus * WAVES * 2;
-    long long fpw = (total + waves - 1) / waves;
-    if (fpw < 16) {
-        const long long oneRound = (total + (long long)cus * WAVES - 1) / ((long long)cus * WAVES);
-        fpw = oneRound < 16 ? oneRound : 16;
-    }
-    const long long usedWaves = (total + fpw - 1) / fpw;
-    const long long blocks = (usedWaves + WAVES - 1) / WAVES;
+    long long fpw;
+    const long long blocks = afx_mel_frames(total, WAVES, &fpw);
     KArgs k;
     memset(&k, 0, sizeof(k));
     k.x = a->x;
@@ -759,15 +545,7 @@ int launch_stft(const AfxStftArgs *a, const float *tab, void *stream) {
     k.binCount = a->binCount;
     k.outPitch = a->outPitch ? a->outPitch : (long long)a->binCount;
     constexpr size_t lds = (size_t)block_lds_bytes(0, 0);
-    static std::atomic<bool> attrSet[AFX_MAX_DEVICES];
-    const int attrDev = afxdev_current_device() & (AFX_MAX_DEVICES - 1);
-    if (!attrSet[attrDev].load(std::memory_order_acquire)) {  // (two threads may both set it: idempotent)
-        AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_stft_band_512<0, 0, false, SHIFT, true, true, MAPPED, FULL>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attrSet[attrDev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((k_stft_band_512<0, 0, false, SHIFT, true, true, MAPPED, FULL>), dim3((unsigned)blocks), dim3(WAVES * 64), lds,
-                       (hipStream_t)stream, k);
+    AFX_LAUNCH_DYN_LDS((k_stft_band_512<0, 0, false, SHIFT, true, true, MAPPED, FULL>), dim3((unsigned)blocks), dim3(WAVES * 64), lds, stream, k);
     AFX_LAUNCH_CHECK("k_stft_band_512<stft>");
     return AFX_OK;
 }
@@ -782,7 +560,7 @@ extern "C" int afxk_stft512(const AfxStftArgs *a, void *stream) {
     const bool two = (a->mode == AFX_SPEC_COMPLEX || a->mode == AFX_SPEC_SQUARE);
     if (!a->outRe || (two && !a->outIm)) return AFX_ERR_ARG;
     if ((long long)a->batch * a->timeLength <= 0) return AFX_OK;
-    const float *tab = stft_tables(stream);
+    const float *tab = afx_device_table<fill_stft_tables>(TAB_BYTES);
     if (!tab) return AFX_ERR_UNSUPPORTED;
     const bool s1 = a->hop == 128;  // register re-use of the overlapping frames
     if (a->mode == AFX_SPEC_COMPLEX) {

@@ -15,6 +15,8 @@
 // (the eight primitives themselves -- inline assembly -- live in afx_asm.h)
 #include <afx_asm.h>
 
+#include "afx_device.h"
+
 // forward 4-point DFT in place: (p0,p1,p2,p3) -> (X0,X1,X2,X3); 8 v_pk_add_f32
 __device__ __forceinline__ void dft4(v2 &p0, v2 &p1, v2 &p2, v2 &p3) {
     const v2 s0 = p0 + p2, s1 = p0 - p2, s2 = p1 + p3, s3 = p1 - p3;
@@ -73,6 +75,21 @@ __host__ __device__ constexpr int rev8(int k) { return 2 * (k & 3) + (k >> 2); }
 __device__ __forceinline__ void wave_lds_order() {
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0), vmcnt/expcnt untouched
     __builtin_amdgcn_wave_barrier();
+}
+
+// what an STFT kernel stores for a spectrum value: AFX_SPEC_* (afx_device.h) -> up to two planes.  Phase:
+// atan2f(im, max(re, 1e-16)) (spectrogram_algorithm.c:1037-1053)
+__device__ __forceinline__ void stft_map(float re, float im, int mode, float normValue, float &v0, float &v1) {
+    v1 = 0.f;
+    switch (mode) {
+        case AFX_SPEC_COMPLEX: v0 = re; v1 = im; break;
+        case AFX_SPEC_POWER: v0 = re * re + im * im; break;
+        case AFX_SPEC_MAG: v0 = sqrtf(re * re + im * im); break;
+        case AFX_SPEC_SQUARE: v0 = re * re - im * im; v1 = 2.f * re * im; break;
+        case AFX_SPEC_MAG_NORM: v0 = powf(sqrtf(re * re + im * im), normValue); break;
+        case AFX_SPEC_PHASE: v0 = atan2f(im, re < 1e-16f ? 1e-16f : re); break;
+        default: v0 = powf(re * re + im * im, normValue); break;  // AFX_SPEC_POWER_NORM
+    }
 }
 
 #endif /* AFX_PKMATH_H */

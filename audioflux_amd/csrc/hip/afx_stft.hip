@@ -44,20 +44,6 @@ __device__ __forceinline__ float2 twn(const float2 *tw, int k, int halfN) {
     return k < halfN ? tw[k] : make_float2(-1.f, 0.f);
 }
 
-// spectrum value of one bin -> up to two planes (re / im); returns the first
-__device__ __forceinline__ void map_bin(float2 c, int mode, float normValue, float &v0, float &v1) {
-    v1 = 0.f;
-    switch (mode) {
-        case AFX_SPEC_COMPLEX: v0 = c.x; v1 = c.y; break;
-        case AFX_SPEC_POWER: v0 = c.x * c.x + c.y * c.y; break;
-        case AFX_SPEC_MAG: v0 = sqrtf(c.x * c.x + c.y * c.y); break;
-        case AFX_SPEC_SQUARE: v0 = c.x * c.x - c.y * c.y; v1 = 2.f * c.x * c.y; break;
-        case AFX_SPEC_MAG_NORM: v0 = powf(sqrtf(c.x * c.x + c.y * c.y), normValue); break;
-        case AFX_SPEC_PHASE: v0 = atan2f(c.y, c.x < 1e-16f ? 1e-16f : c.x); break;
-        default: v0 = powf(c.x * c.x + c.y * c.y, normValue); break;  // AFX_SPEC_POWER_NORM
-    }
-}
-
 // sample q of the (virtually padded) clip
 __device__ __forceinline__ float fetch(const float *x, long long q, const AfxStftArgs &a) {
     if (q >= 0 && q < a.dataLength) return x[q];
@@ -140,7 +126,7 @@ __global__ void k_stft_generic(AfxStftArgs a) {
         float2 c = make_float2(E.x + (w.x * O.x - w.y * O.y), E.y + (w.x * O.y + w.y * O.x));
         if (mirror) c.y = -c.y;
         float v0, v1;
-        map_bin(c, a.mode, a.normValue, v0, v1);
+        stft_map(c.x, c.y, a.mode, a.normValue, v0, v1);
         if (band) {
             prow[j] = v0;
             if (two) prow[a.binCount + j] = v1;
@@ -217,7 +203,7 @@ __global__ __launch_bounds__(SW * 64) void k_stft_wave(AfxStftArgs a, const floa
                     a.outRe[row + j] = X.x;
                     a.outIm[row + j] = X.y;
                 } else {
-                    map_bin(make_float2(X.x, X.y), a.mode, a.normValue, v0, v1);
+                    stft_map(X.x, X.y, a.mode, a.normValue, v0, v1);
                     a.outRe[row + j] = v0;
                     if (two) a.outIm[row + j] = v1;
                 }
@@ -228,7 +214,7 @@ __global__ __launch_bounds__(SW * 64) void k_stft_wave(AfxStftArgs a, const floa
                     a.outRe[row + j2] = X.x;
                     a.outIm[row + j2] = -X.y;
                 } else {
-                    map_bin(make_float2(X.x, -X.y), a.mode, a.normValue, v0, v1);
+                    stft_map(X.x, -X.y, a.mode, a.normValue, v0, v1);
                     a.outRe[row + j2] = v0;
                     if (two) a.outIm[row + j2] = v1;
                 }

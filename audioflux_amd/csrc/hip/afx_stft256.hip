@@ -10,7 +10,6 @@
 
 #include <cstdint>
 #include <cstdlib>
-#include <mutex>
 
 #include "afx_device.h"
 #include "afx_hipcheck.h"
@@ -20,19 +19,6 @@ namespace {
 
 typedef afxws::Fft512 F;  // its 256-point complex core
 constexpr int NW = 12;    // waves per workgroup (12 x 2.5 KB of exchange image, 1 KB of window, 3.7 KB of twiddles)
-
-__device__ __forceinline__ void map_value(float re, float im, int mode, float normValue, float &v0, float &v1) {
-    v1 = 0.f;
-    switch (mode) {
-        case AFX_SPEC_COMPLEX: v0 = re; v1 = im; break;
-        case AFX_SPEC_POWER: v0 = re * re + im * im; break;
-        case AFX_SPEC_MAG: v0 = sqrtf(re * re + im * im); break;
-        case AFX_SPEC_SQUARE: v0 = re * re - im * im; v1 = 2.f * re * im; break;
-        case AFX_SPEC_MAG_NORM: v0 = powf(sqrtf(re * re + im * im), normValue); break;
-        case AFX_SPEC_PHASE: v0 = atan2f(im, re < 1e-16f ? 1e-16f : re); break;
-        default: v0 = powf(re * re + im * im, normValue); break;  // AFX_SPEC_POWER_NORM
-    }
-}
 
 // FULL: complex results, all 256 bins (stftObj_stft's layout): no range checks, no map
 template <bool FULL>
@@ -83,11 +69,11 @@ __global__ __launch_bounds__(NW * 64) void k_stft_256(AfxStftArgs a, const float
                 const int j = k - a.binLo;
                 if (j >= 0 && j < a.binCount) {
                     float v0, v1;
-                    map_value(are, aim, a.mode, a.normValue, v0, v1);
+                    stft_map(are, aim, a.mode, a.normValue, v0, v1);
                     a.outRe[fa * pitch + j] = v0;
                     if (two) a.outIm[fa * pitch + j] = v1;
                     if (fb != fa) {
-                        map_value(bre, bim, a.mode, a.normValue, v0, v1);
+                        stft_map(bre, bim, a.mode, a.normValue, v0, v1);
                         a.outRe[fb * pitch + j] = v0;
                         if (two) a.outIm[fb * pitch + j] = v1;
                     }
@@ -100,26 +86,7 @@ __global__ __launch_bounds__(NW * 64) void k_stft_256(AfxStftArgs a, const float
 
 // twiddle tables of the 256-point core, one device copy per device (never freed)
 const float2 *tables256() {
-    static std::mutex mu;
-    static float2 *dTab[AFX_MAX_DEVICES] = {};
-    const int dev = afxdev_current_device();
-    if (dev < 0 || dev >= AFX_MAX_DEVICES) return nullptr;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!dTab[dev]) {
-        float *h = static_cast<float *>(calloc(2 * F::TAB_F2, sizeof(float)));
-        if (!h) return nullptr;
-        F::fill_tables(h);
-        float2 *d = nullptr;
-        int st = afxdev_malloc(reinterpret_cast<void **>(&d), sizeof(float) * 2 * F::TAB_F2);
-        if (st == AFX_OK && hipMemcpy(d, h, sizeof(float) * 2 * F::TAB_F2, hipMemcpyHostToDevice) != hipSuccess) st = AFX_ERR_HIP;
-        free(h);
-        if (st != AFX_OK) {
-            afxdev_free(d);
-            return nullptr;
-        }
-        dTab[dev] = d;
-    }
-    return dTab[dev];
+    return reinterpret_cast<const float2 *>(afx_device_table<F::fill_tables>(sizeof(float) * 2 * F::TAB_F2));
 }
 
 template <bool FULL>

@@ -345,7 +345,7 @@ int stftObj_istftBatchDevice(STFTObj o, const float *dReal, const float *dImag, 
     a.win2 = o->dWin12 + o->fftLength;
     a.out = dData;
     a.outStride = dataStride;
-    /* n_fft 2048: one launch, overlap-add on the chip, no [frames, N] scratch */
+    /* n_fft 256 ... 4096: one launch, overlap-add on the chip, no [frames, N] scratch */
     if (!afxdev_no_fused()) {
         st = afxk_istft_fused(&a, hipStream);
         if (st != AFX_ERR_UNSUPPORTED) return st;

@@ -142,3 +142,37 @@ def test_split_plan_refuses_what_does_not_fit():
             b = Band()
             assert lib.afx_bandplan_build_split(bank.ctypes.data_as(fp), num, 1025, ta, tb, 1104, C.byref(b)) == 1
             assert b.wA is None or not b.wA  # nothing left allocated
+
+
+# (total frames, CUs, waves per workgroup) -> (frames per wave, workgroups), written down from the launchers' arithmetic
+# before the function was shared: waves per workgroup 16 (n_fft 512 / 1024), 12 (2048, real and complex), 8 (4096)
+FRAME_SPLIT = [((934000, 256, 16), (115, 508)), ((934000, 256, 12), (153, 509)), ((934000, 256, 8), (229, 510)),
+               ((1000, 256, 16), (1, 63)), ((1000, 256, 12), (1, 84)), ((1000, 256, 8), (1, 125)),
+               ((40000, 256, 16), (10, 250)), ((100000, 256, 16), (16, 391)),
+               ((1, 256, 16), (1, 1)), ((1, 256, 12), (1, 1)), ((1, 256, 8), (1, 1)),
+               ((0, 256, 16), (0, 0)), ((0, 256, 12), (0, 0)), ((0, 256, 8), (0, 0))]
+
+
+def test_frame_distribution_of_the_fused_launchers(tmp_path):
+    """afx_frame_split (afx_device.h), compiled as plain C: two rounds of workgroups, short calls spread over every CU"""
+    import os
+    import shutil
+    import subprocess
+    if shutil.which("gcc") is None:
+        pytest.skip("needs gcc")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = tmp_path / "split.c"
+    src.write_text('#include <stdio.h>\n#include <stdlib.h>\n#include "afx_device.h"\n'
+                   "int main(int argc, char **argv) {\n"
+                   "    for (int i = 1; i + 2 < argc; i += 3) {\n"
+                   "        long long fpw = -1;\n"
+                   "        const long long wgs = afx_frame_split(atoll(argv[i]), atoi(argv[i + 1]), atoi(argv[i + 2]), 2, &fpw);\n"
+                   '        printf("%lld %lld\\n", fpw, wgs);\n'
+                   "    }\n    return 0;\n}\n")
+    exe = str(tmp_path / "split")
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", f"-I{root}/include", f"-I{root}/audioflux_amd/csrc/hip", str(src), "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = subprocess.run([exe] + [str(v) for case, _ in FRAME_SPLIT for v in case], capture_output=True, text=True, check=True).stdout
+    got = [tuple(int(v) for v in line.split()) for line in out.splitlines()]
+    assert got == [want for _, want in FRAME_SPLIT]
