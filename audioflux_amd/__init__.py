@@ -8,6 +8,7 @@ from ._lib import LIB_PATH, build, get_lib, last_error, runtime_status
 from .types import *  # noqa: F401,F403
 from .bft import BFT
 from .xxcc import XXCC
+from .spectral import Spectral
 from .cepstrogram import Cepstrogram
 from .cqt import CQT
 from .cwt import CWT
@@ -20,6 +21,6 @@ from .spectrogram import (Bark, BarkSpectrogram, Chroma, Erb, ErbSpectrogram, Li
                           Spectrogram, SpectrogramBase, SpectralFilterBankType)
 from .batch import mel_mfcc_device
 
-__all__ = ["BFT", "XXCC", "Cepstrogram", "CQT", "CWT", "PWT", "Reassign", "STFT", "Synsq", "WSST", "Spectrogram", "SpectrogramBase", "MelSpectrogram", "BarkSpectrogram", "ErbSpectrogram",
+__all__ = ["BFT", "XXCC", "Spectral", "SpectralNoveltyMethodType", "SpectralNoveltyDataType", "Cepstrogram", "CQT", "CWT", "PWT", "Reassign", "STFT", "Synsq", "WSST", "Spectrogram", "SpectrogramBase", "MelSpectrogram", "BarkSpectrogram", "ErbSpectrogram",
            "Linear", "Mel", "Bark", "Erb", "Chroma", "SpectralFilterBankType", "mel_mfcc_device", "get_lib", "build", "runtime_status",
            "last_error", "LIB_PATH"]

@@ -498,6 +498,48 @@ static inline long long afx_frame_split(long long total, int cus, int wavesPerWg
     return (usedWaves + wavesPerWg - 1) / wavesPerWg;
 }
 
+/* ---- spectral descriptors (afx_descriptors.hip) ---------------------------- */
+/* descriptor kinds in the order of AfxSpectralKind (include/afx_batch.h) */
+enum {
+    AFX_DESC_FLATNESS = 0, AFX_DESC_FLUX, AFX_DESC_ROLLOFF, AFX_DESC_CENTROID, AFX_DESC_SPREAD, AFX_DESC_SKEWNESS,
+    AFX_DESC_KURTOSIS, AFX_DESC_ENTROPY, AFX_DESC_CREST, AFX_DESC_SLOPE, AFX_DESC_DECREASE, AFX_DESC_BANDWIDTH,
+    AFX_DESC_RMS, AFX_DESC_ENERGY, AFX_DESC_HFC, AFX_DESC_SD, AFX_DESC_SF, AFX_DESC_MKL, AFX_DESC_PD, AFX_DESC_WPD,
+    AFX_DESC_NWPD, AFX_DESC_CD, AFX_DESC_RCD, AFX_DESC_BROADBAND, AFX_DESC_NOVELTY, AFX_DESC_EEF, AFX_DESC_EER,
+    AFX_DESC_MAX, AFX_DESC_MEAN, AFX_DESC_VAR, AFX_DESC_COUNT
+};
+/* one request: its parameters in the order of the reference prototype, and the first output slot it writes */
+typedef struct {
+    int kind;
+    int iarg[4];
+    float farg[2];
+    int slot;
+} AfxDescReq;
+
+typedef struct {
+    const float *spec;   /* device [rows, num]                                                        */
+    const float *phase;  /* device [rows, num]; pd / wpd / nwpd / cd / rcd only                       */
+    float *out;          /* device: request r writes out[(slot + k) * outStride + row]                */
+    long long rows, outStride;
+    int framesPerClip;   /* > 0: frame-difference descriptors restart every framesPerClip rows        */
+    int num;             /* row pitch                                                                 */
+    int start, len;      /* the edge: bins start .. start + len - 1, or idx[0 .. len - 1]             */
+    const int *idx;      /* device index table (any order, repeats allowed), NULL for a range         */
+    int idx0;            /* first bin of the edge (idx[0] or start)                                   */
+    const float *fre;    /* device [num]                                                              */
+    /* per-edge constants, summed on the host in the reference's order (spectral_algorithm.c:1100-1140,
+     * :1040-1075, flux_spectral.c:353-360): mean of fre over the edge, sum (fre - mean)^2, that / (len - 1) */
+    float meanFre, slopeDen, varFre;
+    int isPower;         /* AFX_DESC_ENERGY: the rows are power already (spectrogram object, dataType Power) */
+    const AfxDescReq *req; /* host; at most one request per kind in a launch */
+    int count;
+} AfxDescArgs;
+/* Row-local kinds in one launch that fetches every row once (rows up to 1024 edge bins stay in registers, longer ones are
+ * read a second time while they sit in L2), frame-difference kinds in a second launch on the same stream.  AFX_ERR_ARG
+ * for a bad kind, two requests of one kind, or a phase kind without `phase`. */
+int afxk_descriptors(const AfxDescArgs *a, void *stream);
+/* out[r, j] = in[r, j] / value, halved at j == 0 and j == halfBin (spectrogram_algorithm.c:2080-2120); in == out allowed */
+int afxk_desc_preprocess(const float *in, float *out, long long rows, int num, float value, int halfBin, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

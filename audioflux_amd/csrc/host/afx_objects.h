@@ -67,6 +67,26 @@ struct OpaqueXXCC {
     int status;
 };
 
+/* the spectral-descriptor object (afx_descriptor.c, feature/spectral_algorithm.h) */
+struct OpaqueSpectral {
+    int num;
+    int timeLength;
+    float *freBandArr;  /* host copy [num] */
+    float *dFre;        /* device [num] */
+    int *indexArr;      /* host: the edge, indexLength entries (owned) */
+    int indexLength;
+    int start, end;     /* first / last entry of indexArr */
+    int isRange;        /* indexArr is start .. end: the kernels need no index table */
+    int *dIndex;        /* device copy of indexArr for an index-list edge */
+    size_t capIndex;
+    float meanFre, slopeDen, varFre; /* per-edge constants of slope / mean / var, summed in the reference's order */
+    int isPower;        /* energy: rows are power already (the spectrogram object's dataType) */
+    void *stream;
+    float *dIn, *dPhase, *dOut; /* grow-only device buffers of the host-pointer calls */
+    size_t capIn, capPhase, capOut;
+    int status;
+};
+
 struct OpaqueSTFT {
     int fftLength, radix2Exp, slideLength;
     WindowType windowType;
@@ -143,6 +163,11 @@ void afx_bft_free_fast(struct OpaqueBFT *o);
 int afx_bft_run_device(struct OpaqueBFT *o, const float *dData, int batch, int dataLength,
                        long long clipStride, float *dRe, float *dIm, float *dTemporal,
                        void *stream);
+
+/* afx_spectrogram.c: the descriptor object a spectrogram object owns (built on first use over its num bands and
+ * freBandArr, isPower from its dataType) and the frame count of its last spectrogram call; NULL on failure (reported) */
+struct OpaqueSpectrogram;
+struct OpaqueSpectral *afx_spectrogram_descriptor(struct OpaqueSpectrogram *o, const char *who, int *timeLength);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,7 @@
 #include "afx_device.h"
 #include "afx_host.h"
 #include "afx_objects.h"
+#include "feature/spectral_algorithm.h"
 #include "spectrogram_algorithm.h"
 
 struct OpaqueSpectrogram {
@@ -47,6 +48,7 @@ struct OpaqueSpectrogram {
     float *dFold;            /* log-chroma: device [num, baseNum] 0/1 fold matrix */
     struct OpaqueSTFT tail;  /* host-only: the streaming tail state machine (afx_stft.c) */
     XXCCObj xxcc;            /* lazily built cepstra plan over num bands */
+    struct OpaqueSpectral *desc; /* lazily built descriptor object over num bands (afx_descriptor.c) */
     float *dDevTw;           /* deconv: twiddles of the 2^devRadix transform */
     int devRadix;
     /* grow-only device scratch of the host-pointer calls */
@@ -694,6 +696,57 @@ void spectrogramObj_deconv(SpectrogramObj o, float *mDataArr1, float *mDataArr2,
     if (st != AFX_OK) fail(o, st, "spectrogramObj_deconv");
 }
 
+/* ---- spectral descriptors: the object owns one descriptor state; the descriptor entry points themselves are in
+ * afx_descriptor.c, next to the spectralObj_* ones they share their internals with */
+struct OpaqueSpectral *afx_spectrogram_descriptor(SpectrogramObj o, const char *who, int *timeLength) {
+    if (!o) {
+        afxdev_set_error("%s: NULL object", who);
+        return NULL;
+    }
+    if (!o->desc) {
+        AFX_ENTER(o->core);
+        const int st = spectralObj_new(&o->desc, o->num, o->freBandArr);
+        if (st != 0) {
+            o->desc = NULL;
+            fail(o, st < -1 ? st : AFX_ERR_ARG, who);
+            return NULL;
+        }
+        /* spectrogram_algorithm.c:2648-2662: energy takes power rows as they are */
+        o->desc->isPower = o->dataType == SpectralData_Power;
+    }
+    if (timeLength) *timeLength = o->timeLength;
+    return o->desc;
+}
+
+/* spectrogram_algorithm.c:2080-2120: rows / (window sum / 2 | (window sum)^2 / 2), bins 0 and fftLength / 2 halved */
+void spectrogramObj_preprocess(SpectrogramObj o, float *mDataArr1, float *mDataArr3) {
+    if (!o) {
+        afxdev_set_error("spectrogramObj_preprocess: NULL object");
+        return;
+    }
+    AFX_ENTER(o->core);
+    if (!mDataArr1 || o->timeLength <= 0) return;
+    float *dst = mDataArr3 ? mDataArr3 : mDataArr1;
+    float *w = afx_window_fft(o->windowType, o->fftLength);
+    if (!w) {
+        fail(o, AFX_ERR_NOMEM, "spectrogramObj_preprocess");
+        return;
+    }
+    float value = 0;
+    for (int i = 0; i < o->fftLength; i++) value += w[i];
+    free(w);
+    if (o->dataType == SpectralData_Mag) value *= 0.5f;
+    else if (o->dataType == SpectralData_Power) value = 0.5f * value * value;
+    const size_t bytes = sizeof(float) * (size_t)o->timeLength * o->num;
+    void *stream = o->core->stream;
+    int st = afxdev_reserve((void **)&o->dTmp, &o->capTmp, bytes);
+    if (st == AFX_OK) st = afxdev_h2d(o->dTmp, mDataArr1, bytes, stream);
+    if (st == AFX_OK) st = afxk_desc_preprocess(o->dTmp, o->dTmp, o->timeLength, o->num, value, o->fftLength / 2, stream);
+    if (st == AFX_OK) st = afxdev_d2h(dst, o->dTmp, bytes, stream);
+    if (st == AFX_OK) st = afxdev_stream_sync(stream);
+    if (st != AFX_OK) fail(o, st, "spectrogramObj_preprocess");
+}
+
 void spectrogramObj_free(SpectrogramObj o) {
     if (!o) return;
     if (o->core && o->core->stream) afxdev_stream_sync(o->core->stream);
@@ -704,6 +757,7 @@ void spectrogramObj_free(SpectrogramObj o) {
     afxdev_free(o->dTmp);
     afxdev_free(o->dSpec);
     xxccObj_free(o->xxcc);
+    spectralObj_free(o->desc);
     bftObj_free(o->core);
     free(o->tail.tailDataArr);
     free(o->freBandArr);

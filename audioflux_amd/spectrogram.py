@@ -10,6 +10,7 @@ from ctypes import POINTER, c_float, c_int, c_longlong, c_void_p
 import numpy as np
 
 from . import _lib, _util
+from .spectral import DescriptorMixin
 from .types import (CepstralRectifyType, ChromaDataNormalType, SpectralDataType,
                     SpectralFilterBankNormalType, SpectralFilterBankScaleType, SpectralFilterBankStyleType,
                     WindowType)
@@ -23,7 +24,9 @@ _OCTAVE_LIKE = (SpectralFilterBankScaleType.OCTAVE, SpectralFilterBankScaleType.
                 SpectralFilterBankScaleType.DEEP_CHROMA)
 
 
-class SpectrogramBase:
+class SpectrogramBase(DescriptorMixin):
+    _prefix = "spectrogramObj"
+
     def __init__(self, num=0, samplate=32000, low_fre=None, high_fre=None, bin_per_octave=12, radix2_exp=12,
                  window_type=None, slide_length=None, data_type=SpectralDataType.POWER,
                  filter_bank_type=SpectralFilterBankScaleType.LINEAR,
@@ -141,12 +144,49 @@ class SpectrogramBase:
             spec = np.zeros((t, self.num), np.float32)
             ph = np.zeros((t, self.num), np.float32) if is_phase_arr else None
             fn(self._obj, _util.fptr(clips[i]), n, _util.fptr(spec), _util.fptr(ph) if is_phase_arr else None)
+            self._last_time_length = t
             specs.append(spec)
             phases.append(ph)
         out = np.ascontiguousarray(np.swapaxes(_util.restore_leading(np.stack(specs), lead), -1, -2))
         if is_phase_arr:
             return out, np.ascontiguousarray(np.swapaxes(_util.restore_leading(np.stack(phases), lead), -1, -2))
         return out
+
+    # ---- descriptors: the C side works on the frame count of the LAST spectrogram call
+    def _before(self, time_length):
+        t = getattr(self, "_last_time_length", None)
+        if t is None:
+            raise ValueError("call spectrogram() first: the descriptors work on the frames of the last spectrogram call")
+        if time_length != t:
+            raise ValueError(f"the descriptor input has {time_length} frames, the last spectrogram call produced {t}")
+
+    def flux(self, m_data_arr, step=1, p=2, is_positive=False, is_no_exp=True, tp=0):
+        """python/audioflux/spectrogram.py:624-680: the reference's spectrogram wrapper hands `is_no_exp` to the C isExp
+        argument as it is, so its default (True) takes the p-th root of the sum -- unlike Spectral.flux (is_exp=False)"""
+        return self._run("flux", m_data_arr, [c_int, c_float, c_int, POINTER(c_int), POINTER(c_int)],
+                         [int(step), float(p), int(is_positive), _util.opt_int(int(is_no_exp)), _util.opt_int(int(tp))])
+
+    def broadband(self, m_data_arr, threshold):
+        """python/audioflux/spectrogram.py:1461: no default threshold on the spectrogram classes"""
+        return super().broadband(m_data_arr, threshold)
+
+    def preprocess(self, m_data_arr_1, m_data_arr_3=None):
+        """(num, time) result of the last spectrogram call, normalised by the window sum for the descriptors
+        (spectrogramObj_preprocess); m_data_arr_3: optional (num, time) float32 array that receives the result too"""
+        m = _util.as_f32(np.swapaxes(np.asarray(m_data_arr_1), -1, -2))
+        if m.ndim != 2 or m.shape[1] != self.num:
+            raise ValueError(f"m_data_arr_1 must be ({self.num}, time)")
+        self._before(m.shape[0])
+        out = np.zeros_like(m)
+        fn = self._lib.spectrogramObj_preprocess
+        fn = _lib.checked(fn)
+        fn.restype = None
+        fn.argtypes = [c_void_p, _util.c_float_p, _util.c_float_p]
+        fn(self._obj, _util.fptr(m), _util.fptr(out))
+        res = np.ascontiguousarray(out.T)
+        if m_data_arr_3 is not None:
+            m_data_arr_3[...] = res
+        return res
 
     def spectrogram_from_stft(self, m_real_arr, m_imag_arr, is_phase_arr=False):
         """spectrogramObj_spectrogram1: a caller-supplied STFT (time, fft_length) re / im -> (num, time)"""
@@ -160,6 +200,7 @@ class SpectrogramBase:
         fn.restype = None
         fn.argtypes = [c_void_p, _util.c_float_p, _util.c_float_p, c_int, c_int, _util.c_float_p, _util.c_float_p]
         fn(self._obj, _util.fptr(re), _util.fptr(im), t, m, _util.fptr(spec), _util.fptr(ph) if is_phase_arr else None)
+        self._last_time_length = t
         return (np.ascontiguousarray(spec.T), np.ascontiguousarray(ph.T)) if is_phase_arr else np.ascontiguousarray(spec.T)
 
     def spectrogram_device(self, x, out=None, stream=None):

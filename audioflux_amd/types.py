@@ -73,6 +73,18 @@ class CepstralRectifyType(IntEnum):
     CUBIC_ROOT = 1
 
 
+class SpectralNoveltyMethodType(IntEnum):
+    SUB = 0
+    ENTROY = 1
+    KL = 2
+    IS = 3
+
+
+class SpectralNoveltyDataType(IntEnum):
+    VALUE = 0
+    NUMBER = 1
+
+
 class CepstralEnergyType(IntEnum):
     REPLACE = 0
     APPEND = 1

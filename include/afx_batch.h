@@ -19,6 +19,7 @@
 #include "cepstrogram_algorithm.h"
 #include "cqt_algorithm.h"
 #include "cwt_algorithm.h"
+#include "feature/spectral_algorithm.h"
 #include "feature/xxcc_algorithm.h"
 #include "pwt_algorithm.h"
 #include "reassign_algorithm.h"
@@ -200,6 +201,32 @@ int afx_comm_world_size(AfxCommObj comm);
 int afx_comm_rank(AfxCommObj comm);
 int afx_gather(AfxCommObj comm, const float *dSend, long long count, float *dRecv, int root, void *hipStream);
 void afx_comm_free(AfxCommObj comm);
+
+/* ---- spectral descriptors of rows that already live in HBM: one call, any list of descriptors, one pass over the rows */
+typedef enum { AFX_SD_FLATNESS = 0, AFX_SD_FLUX, AFX_SD_ROLLOFF, AFX_SD_CENTROID, AFX_SD_SPREAD, AFX_SD_SKEWNESS,
+               AFX_SD_KURTOSIS, AFX_SD_ENTROPY, AFX_SD_CREST, AFX_SD_SLOPE, AFX_SD_DECREASE, AFX_SD_BANDWIDTH, AFX_SD_RMS,
+               AFX_SD_ENERGY, AFX_SD_HFC, AFX_SD_SD, AFX_SD_SF, AFX_SD_MKL, AFX_SD_PD, AFX_SD_WPD, AFX_SD_NWPD, AFX_SD_CD,
+               AFX_SD_RCD, AFX_SD_BROADBAND, AFX_SD_NOVELTY, AFX_SD_EEF, AFX_SD_EER, AFX_SD_MAX, AFX_SD_MEAN, AFX_SD_VAR,
+               AFX_SD_COUNT } AfxSpectralKind;
+/* iarg / farg carry the descriptor's own parameters in the order of its reference prototype (flux: step, isPostive,
+ * isExp, type / p; rolloff: / threshold; entropy, eef: isNorm; eer: isNorm / gamma; bandWidth: / p; energy: isLog / gamma;
+ * sd, sf: step, isPostive; mkl: type; broadband: / threshold; novelty: step, methodType, dataType / threshold); unused
+ * entries 0 */
+typedef struct { int kind; int iarg[4]; float farg[2]; } AfxSpectralRequest;
+
+/* dSpec (and dPhase, needed by pd / wpd / nwpd / cd / rcd only) [rows, num] in HBM -> dOut[slot * outStride + row].  A request
+ * takes one slot, MAX / MEAN / VAR two (value, then frequency).  framesPerClip > 0: the rows are clips of that many frames and the
+ * frame-difference descriptors restart at every clip (their first `step` frames are 0), exactly as a loop of per-clip calls;
+ * 0: one clip.  Asynchronous on hipStream.  Uses the object's edge (spectralObj_setEdge / setEdgeArr): synchronise
+ * hipStream before changing the edge, the kernels read its index table while they run.  The row-local
+ * descriptors of the list share one launch that fetches every row once, the frame-difference ones a second launch; a kind
+ * asked for twice (other parameters) costs one more pass.  AFX_ERR_ARG: count <= 0, a kind outside AfxSpectralKind, a
+ * phase descriptor without dPhase, outStride < rows. */
+int spectralObj_computeDevice(SpectralObj spectralObj, const float *dSpec, const float *dPhase, long long rows,
+                              int framesPerClip, const AfxSpectralRequest *requests, int count, float *dOut,
+                              long long outStride, void *hipStream);
+/* how many output slots a request list needs (AFX_ERR_ARG for a bad list) */
+int afx_spectralSlots(const AfxSpectralRequest *requests, int count);
 
 #ifdef __cplusplus
 }

@@ -73,6 +73,20 @@ typedef enum {
     SpectralFilterBankNormal_BandWidth = 2
 } SpectralFilterBankNormalType;
 
+/* per-bin term of the spectral novelty (reference flux_base.h:103-110; "Entroy" is the reference's spelling) */
+typedef enum {
+    SpectralNoveltyMethod_Sub = 0,
+    SpectralNoveltyMethod_Entroy = 1,
+    SpectralNoveltyMethod_KL = 2,
+    SpectralNoveltyMethod_IS = 3
+} SpectralNoveltyMethodType;
+
+/* what the novelty adds up: the terms above the threshold, or how many there are (reference flux_base.h:112-116) */
+typedef enum {
+    SpectralNoveltyData_Value = 0,
+    SpectralNoveltyData_Number = 1
+} SpectralNoveltyDataType;
+
 /* per-frame chroma normalisation (reference flux_base.h:117-127) */
 typedef enum {
     ChromaDataNormal_None = 0,

@@ -10,9 +10,11 @@
  * python/audioflux/spectrogram.py.  Execution: the kernels of the BFT path (fused STFT ->
  * banded filter bank, size-generic STFT, MFMA GEMM, MFMA cepstra) plus k_spec_map / k_row_post.
  *
+ * The spectral descriptors of the result (spectrogramObj_flatness ... spectrogramObj_var) forward to
+ * the descriptor object of feature/spectral_algorithm.h, which the spectrogram object owns.
+ *
  * Not provided by this backend: the "deep" salience scales (newDeep /
- * newDeepChroma return -4) and the spectral-descriptor family (flatness ... novelty), which the
- * wrapper resolves lazily and which are outside the batched time-frequency path.
+ * newDeepChroma return -4).
  */
 #ifndef SPECTROGRAM_ALGORITHM_H
 #define SPECTROGRAM_ALGORITHM_H
@@ -88,6 +90,50 @@ void spectrogramObj_xxccStandard(SpectrogramObj spectrogramObj, float *mDataArr1
 /* mDataArr1 [T, num] -> timbre (formant) mDataArr2, pitch mDataArr3, both [T, num].
  * replaces spectrogram_algorithm.c:1546-1612 */
 void spectrogramObj_deconv(SpectrogramObj spectrogramObj, float *mDataArr1, float *mDataArr2, float *mDataArr3);
+
+/* ---- spectral descriptors of a result of spectrogramObj_spectrogram (src/spectrogram_algorithm.h:123-182,
+ * src/spectrogram_algorithm.c:2020-3027).  Delegation: the object owns one descriptor object
+ * (feature/spectral_algorithm.h, where every descriptor is defined) over its num bands and freBandArr; timeLength is that
+ * of the last spectrogramObj_spectrogram call; spectrogramObj_energy takes power rows as they are when the object's
+ * dataType is Power (spectrogram_algorithm.c:2648-2662; spectralObj_energy always squares). */
+/* start / end count the object's bands 0 .. num - 1.  replaces spectrogram_algorithm.c:2020-2046 */
+void spectrogramObj_setEdge(SpectrogramObj spectrogramObj, int start, int end);
+/* takes ownership of the calloc'ed indexArr.  replaces spectrogram_algorithm.c:2048-2078 */
+void spectrogramObj_setEdgeArr(SpectrogramObj spectrogramObj, int *indexArr, int indexLength);
+/* mDataArr1 [T, num] / (sum of the window / 2: magnitude; (sum)^2 / 2: power), bins 0 and fftLength / 2 halved, into
+ * mDataArr3 (NULL: in place).  replaces spectrogram_algorithm.c:2080-2120 */
+void spectrogramObj_preprocess(SpectrogramObj spectrogramObj, float *mDataArr1, float *mDataArr3);
+
+void spectrogramObj_flatness(SpectrogramObj spectrogramObj, float *mDataArr, float *dataArr);
+void spectrogramObj_flux(SpectrogramObj spectrogramObj, float *mDataArr, int step, float p, int isPostive, int *isExp, int *type, float *dataArr);
+void spectrogramObj_rolloff(SpectrogramObj spectrogramObj, float *mDataArr, float threshold, float *dataArr);
+void spectrogramObj_centroid(SpectrogramObj spectrogramObj, float *mDataArr, float *dataArr);
+void spectrogramObj_spread(SpectrogramObj spectrogramObj, float *mDataArr, float *dataArr);
+void spectrogramObj_skewness(SpectrogramObj spectrogramObj, float *mDataArr, float *dataArr);
+void spectrogramObj_kurtosis(SpectrogramObj spectrogramObj, float *mDataArr, float *dataArr);
+void spectrogramObj_entropy(SpectrogramObj spectrogramObj, float *mDataArr, int isNorm, float *dataArr);
+void spectrogramObj_crest(SpectrogramObj spectrogramObj, float *mDataArr, float *dataArr);
+void spectrogramObj_slope(SpectrogramObj spectrogramObj, float *mDataArr, float *dataArr);
+void spectrogramObj_decrease(SpectrogramObj spectrogramObj, float *mDataArr, float *dataArr);
+void spectrogramObj_bandWidth(SpectrogramObj spectrogramObj, float *mDataArr, float p, float *dataArr);
+void spectrogramObj_rms(SpectrogramObj spectrogramObj, float *mDataArr, float *dataArr);
+void spectrogramObj_energy(SpectrogramObj spectrogramObj, float *mDataArr, int isLog, float gamma, float *dataArr);
+void spectrogramObj_hfc(SpectrogramObj spectrogramObj, float *mDataArr, float *dataArr);
+void spectrogramObj_sd(SpectrogramObj spectrogramObj, float *mDataArr, int step, int isPostive, float *dataArr);
+void spectrogramObj_sf(SpectrogramObj spectrogramObj, float *mDataArr, int step, int isPostive, float *dataArr);
+void spectrogramObj_mkl(SpectrogramObj spectrogramObj, float *mDataArr, int type, float *dataArr);
+void spectrogramObj_pd(SpectrogramObj spectrogramObj, float *mSpecArr, float *mPhaseArr, float *dataArr);
+void spectrogramObj_wpd(SpectrogramObj spectrogramObj, float *mSpecArr, float *mPhaseArr, float *dataArr);
+void spectrogramObj_nwpd(SpectrogramObj spectrogramObj, float *mSpecArr, float *mPhaseArr, float *dataArr);
+void spectrogramObj_cd(SpectrogramObj spectrogramObj, float *mSpecArr, float *mPhaseArr, float *dataArr);
+void spectrogramObj_rcd(SpectrogramObj spectrogramObj, float *mSpecArr, float *mPhaseArr, float *dataArr);
+void spectrogramObj_broadband(SpectrogramObj spectrogramObj, float *mDataArr, float threshold, float *dataArr);
+void spectrogramObj_novelty(SpectrogramObj spectrogramObj, float *mDataArr, int step, float threshold, SpectralNoveltyMethodType *methodType, SpectralNoveltyDataType *dataType, float *dataArr);
+void spectrogramObj_eef(SpectrogramObj spectrogramObj, float *mDataArr, int isNorm, float *dataArr);
+void spectrogramObj_eer(SpectrogramObj spectrogramObj, float *mDataArr, int isNorm, float gamma, float *dataArr);
+void spectrogramObj_max(SpectrogramObj spectrogramObj, float *mDataArr, float *valueArr, float *freArr);
+void spectrogramObj_mean(SpectrogramObj spectrogramObj, float *mDataArr, float *valueArr, float *freArr);
+void spectrogramObj_var(SpectrogramObj spectrogramObj, float *mDataArr, float *valueArr, float *freArr);
 
 /* NULL-safe.  replaces spectrogram_algorithm.c:3029-3169 */
 void spectrogramObj_free(SpectrogramObj spectrogramObj);
