@@ -540,6 +540,29 @@ int afxk_descriptors(const AfxDescArgs *a, void *stream);
 /* out[r, j] = in[r, j] / value, halved at j == 0 and j == halfBin (spectrogram_algorithm.c:2080-2120); in == out allowed */
 int afxk_desc_preprocess(const float *in, float *out, long long rows, int num, float value, int halfBin, void *stream);
 
+/* ---- harmonic / percussive separation (afx_hpss.hip) ----------------------- */
+typedef struct {
+    const float *re, *im;  /* device half spectrum [rows, pitch]: bins 0 .. cols - 1 of every frame               */
+    long long rows;        /* clips * framesPerClip (the last clip may be shorter)                                */
+    int framesPerClip;     /* > 0: a median along time never reads across a clip boundary                         */
+    int cols, pitch;       /* bins per frame (fftLength / 2 + 1 when spectra are stored), floats between rows     */
+    int hOrder, pOrder;    /* odd, 1 ... 63: window along time / along frequency; zeros outside the clip's plane  */
+    int fftLength;
+    float *hRe, *hIm;      /* device [rows, fftLength] or NULL: the harmonic spectrum with its Hermitian mirror   */
+    float *pRe, *pIm;      /* the percussive one                                                                  */
+    float *hMag, *pMag;    /* device [rows, cols] or NULL: the masked magnitudes                                  */
+} AfxHpssArgs;
+/* mag = sqrtf(re^2 + im^2); h, p = medians of mag along time / frequency; H = h^2 / max(h^2 + p^2, 1e-16) mag, P likewise;
+ * spectra = H, P times the unit phase (re, im) / max(mag, 1e-16) (hpss_algorithm.c:168-300).  One launch, nothing but the
+ * requested outputs is written.  AFX_ERR_UNSUPPORTED for an order it does not cover. */
+int afxk_hpss_mask(const AfxHpssArgs *a, void *stream);
+/* out[r, c] = median of the odd `order` values of in [rows, cols] around (r, c) along axis 0 (rows, inside the clip of
+ * framesPerClip rows; 0: one clip) or axis 1, zeros outside; exact selection.  Orders up to AFX_MEDIAN_FAST_ORDER keep the
+ * window sorted in registers, up to AFX_MEDIAN_MAX_ORDER a rank-counting kernel runs; beyond: AFX_ERR_UNSUPPORTED */
+#define AFX_MEDIAN_FAST_ORDER 63
+#define AFX_MEDIAN_MAX_ORDER 255
+int afxk_median_filter(const float *in, long long rows, int cols, int framesPerClip, int axis, int order, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

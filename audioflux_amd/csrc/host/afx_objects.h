@@ -126,6 +126,21 @@ struct OpaqueReassign {
     int lastStreamSet, status;
 };
 
+/* the harmonic / percussive separation object (afx_hpss.c, mir/hpss_algorithm.h) */
+struct OpaqueHPSS {
+    struct OpaqueSTFT *stft; /* owned: Hamm by default, hop fftLength/4, no padding, not continuing; its stream is the object's */
+    int radix2Exp, fftLength, slideLength;
+    int hOrder, pOrder;
+    void *stream;
+    float *dSpec;            /* grow-only chunk scratch: half spectrum re | im, then the full spectra of the outputs */
+    size_t capSpec;
+    float *dX, *dH, *dP;     /* grow-only device buffers of the host-pointer call */
+    size_t capX, capH, capP;
+    void *lastStream;        /* stream of the previous launch (the scratch is shared) */
+    int lastStreamSet;
+    int status;
+};
+
 /* framing state machine of a legacy stftObj_stft call, host fields of the object only
  * (afx_stft.c; also used by the spectrogram object for its isContinue mode) */
 int afx_stft_deal_data(struct OpaqueSTFT *o, const float *dataArr, int dataLength, int *valid,

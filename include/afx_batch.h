@@ -21,6 +21,7 @@
 #include "cwt_algorithm.h"
 #include "feature/spectral_algorithm.h"
 #include "feature/xxcc_algorithm.h"
+#include "mir/hpss_algorithm.h"
 #include "pwt_algorithm.h"
 #include "reassign_algorithm.h"
 #include "spectrogram_algorithm.h"
@@ -227,6 +228,26 @@ int spectralObj_computeDevice(SpectralObj spectralObj, const float *dSpec, const
                               long long outStride, void *hipStream);
 /* how many output slots a request list needs (AFX_ERR_ARG for a bad list) */
 int afx_spectralSlots(const AfxSpectralRequest *requests, int count);
+
+/* ---- harmonic / percussive separation of clips that already live in HBM (mir/hpss_algorithm.h) -----------------------
+ * batch clips of dataLength samples -> dH / dP [b * outStride + j], j < hpssObj_calDataLength(dataLength); read-modify-write
+ * like hpssObj_hpss (zero them for the plain result); dH or dP may be NULL (that output and its inverse are skipped).
+ * Asynchronous on hipStream, no hidden synchronisation in the steady state.  Large batches run in chunks of whole clips so that
+ * the object's spectrum scratch stays bounded (AFX_HPSS_CHUNK_MB, default 1024); the scratch grows on the first call that needs
+ * it and is reused.  0 frames (dataLength < fftLength): nothing is written.  AFX_ERR_ARG: NULL object / input, both outputs NULL,
+ * batch <= 0, outStride < hpssObj_calDataLength(dataLength). */
+int hpssObj_hpssBatchDevice(HPSSObj hpssObj, const float *dData, int batch, int dataLength, long long clipStride, float *dH,
+                            float *dP, long long outStride, void *hipStream);
+/* the masked magnitude planes alone, dHMag / dPMag [batch][T, fftLength/2 + 1], no inverse transform: what a feature pipeline
+ * (mel of the harmonic part, descriptors of the percussive part) reads; either may be NULL.  Plain stores. */
+int hpssObj_spectraBatchDevice(HPSSObj hpssObj, const float *dData, int batch, int dataLength, long long clipStride, float *dHMag,
+                               float *dPMag, void *hipStream);
+/* the primitive: 1-D median of odd `order` (1 ... 255) along axis 0 (rows; never across a clip boundary: framesPerClip > 0 cuts
+ * the rows into clips, 0 = one clip) or axis 1 (columns) of resident dIn [rows, cols] -> dOut [rows, cols], zeros outside the
+ * plane.  Exact selection: the output is bit for bit the middle element of the sorted window.  In place is not allowed.
+ * AFX_ERR_UNSUPPORTED (-4): even order or order > 255; AFX_ERR_ARG: bad pointers / sizes / axis. */
+int afx_medianFilterDevice(const float *dIn, long long rows, int cols, int framesPerClip, int axis, int order, float *dOut,
+                           void *hipStream);
 
 #ifdef __cplusplus
 }
