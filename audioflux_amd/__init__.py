@@ -16,12 +16,13 @@ from .pwt import PWT
 from .reassign import Reassign
 from .stft import STFT
 from .hpss import HPSS, median_filter_device
+from .pitch import PitchYIN
 from .synsq import Synsq
 from .wsst import WSST
 from .spectrogram import (Bark, BarkSpectrogram, Chroma, Erb, ErbSpectrogram, Linear, Mel, MelSpectrogram,
                           Spectrogram, SpectrogramBase, SpectralFilterBankType)
 from .batch import mel_mfcc_device
 
-__all__ = ["BFT", "XXCC", "Spectral", "SpectralNoveltyMethodType", "SpectralNoveltyDataType", "Cepstrogram", "CQT", "CWT", "PWT", "Reassign", "STFT", "HPSS", "median_filter_device", "Synsq", "WSST", "Spectrogram", "SpectrogramBase", "MelSpectrogram", "BarkSpectrogram", "ErbSpectrogram",
+__all__ = ["BFT", "XXCC", "Spectral", "SpectralNoveltyMethodType", "SpectralNoveltyDataType", "Cepstrogram", "CQT", "CWT", "PWT", "Reassign", "STFT", "HPSS", "median_filter_device", "PitchYIN", "Synsq", "WSST", "Spectrogram", "SpectrogramBase", "MelSpectrogram", "BarkSpectrogram", "ErbSpectrogram",
            "Linear", "Mel", "Bark", "Erb", "Chroma", "SpectralFilterBankType", "mel_mfcc_device", "get_lib", "build", "runtime_status",
            "last_error", "LIB_PATH"]

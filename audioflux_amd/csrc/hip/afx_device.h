@@ -563,6 +563,31 @@ int afxk_hpss_mask(const AfxHpssArgs *a, void *stream);
 #define AFX_MEDIAN_MAX_ORDER 255
 int afxk_median_filter(const float *in, long long rows, int cols, int framesPerClip, int axis, int order, float *out, void *stream);
 
+/* ---- YIN pitch tracking (afx_pitch_yin.hip) -------------------------------- */
+typedef struct {
+    const float *x;        /* device, clip b starts at x + b * clipStride                                         */
+    long long clipStride;  /* in samples                                                                          */
+    int batch, dataLength; /* clips, samples per clip                                                             */
+    int timeLength;        /* frames per clip: (dataLength - fftLength) / hop + 1 > 0                             */
+    int radix2Exp, hop;    /* fftLength = 2^radix2Exp, 6 ... 13; hop > 0 (may exceed fftLength)                   */
+    int autoLength;        /* 0 ... fftLength - 1: the correlation sums autoLength + 1 products                   */
+    int minIndex, maxIndex; /* lags of the curve: 1 <= minIndex, minIndex + 2 <= maxIndex <= fftLength - autoLength - 1 */
+    int samplate;
+    float thresh;
+    const float *twiddle;  /* device float2 (cos, -sin)(2 pi m / fftLength), m < fftLength / 2                    */
+    float *fre, *trough, *minv; /* device [b * outStride + t] or NULL: 0 in fre / trough where no trough qualifies */
+    long long outStride;
+    float *candFre, *candVal; /* device [row * candPitch + i], row = b * timeLength + t, or NULL (both or none)    */
+    int *candLen;          /* device [row]: all qualifying troughs of the frame; the first candPitch are stored    */
+    int candPitch;
+    float *curve;          /* device [row * yinLength + k], yinLength = maxIndex - minIndex + 1, or NULL           */
+} AfxPitchYinArgs;
+/* One launch from samples to results (_pitch_yin.c:352-603): difference function by an FFT autocorrelation, cumulative-mean
+ * normalisation, first trough below thresh with its parabolic offset, min of the curve; optionally the candidate lists and
+ * the curve.  One workgroup per frame, everything between the samples and the outputs stays in LDS and registers.
+ * AFX_ERR_ARG for a plan outside the limits above, AFX_ERR_UNSUPPORTED beyond 2^31 - 1 frames in a launch. */
+int afxk_pitch_yin(const AfxPitchYinArgs *a, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

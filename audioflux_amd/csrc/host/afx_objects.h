@@ -4,6 +4,7 @@
 
 #include <stddef.h>
 
+#include "afx_frametail.h"
 #include "flux_base.h"
 #include "reassign_algorithm.h"
 
@@ -138,6 +139,26 @@ struct OpaqueHPSS {
     size_t capX, capH, capP;
     void *lastStream;        /* stream of the previous launch (the scratch is shared) */
     int lastStreamSet;
+    int status;
+};
+
+/* the YIN pitch tracker (afx_pitch_yin.c, mir/_pitch_yin.h) */
+struct OpaquePitchYIN {
+    int radix2Exp, fftLength, slideLength, autoLength;
+    int minIndex, maxIndex, diffLength, yinLength; /* lags of the curve: minIndex ... maxIndex < diffLength = fftLength - autoLength */
+    int samplate;
+    float thresh;
+    int isDebug;
+    AfxFrameTail tail;       /* isContinue and the samples carried between host-pointer calls */
+    int timeLength;          /* frames of the last pitchYINObj_pitch call */
+    void *stream;
+    float *dTwiddle;
+    float *dX, *dOut, *dCand; /* grow-only device buffers of the host-pointer call: samples, [3][T], [2][T, mLen] + lengths */
+    size_t capX, capOut, capCand;
+    float *hOut;             /* host staging [3][T] */
+    float *mFreArr, *mTroughArr; /* host [T, mLen]: pitchYINObj_getTroughData */
+    int *lenArr;
+    size_t capHost;          /* frames the host arrays hold */
     int status;
 };
 

@@ -1,0 +1,126 @@
+"""PitchYIN -- ctypes mirror of the reference wrapper class (python/audioflux/mir/pitch_yin.py:10-150) over
+libaudioflux_mi355x.so: same constructor arguments and defaults, `set_thresh`, `cal_time_length`, `pitch` ->
+(fre_arr, value1_arr, value2_arr).  All leading axes of the input go through ONE batched call where the reference loops over
+channels.  Extra: device-resident calls on torch tensors (`pitch_device`, `troughs_device`, `curve_device`)."""
+import ctypes
+from ctypes import POINTER, c_float, c_int, c_longlong, c_void_p
+
+import numpy as np
+
+from . import _lib, _util
+
+
+class PitchYIN:
+    def __init__(self, samplate=32000, low_fre=27.0, high_fre=2000.0, radix2_exp=12, slide_length=1024, auto_length=2048):
+        self._lib = _lib.get_lib()
+        self._obj = c_void_p(None)
+        self.samplate, self.low_fre, self.high_fre = samplate, low_fre, high_fre
+        self.radix2_exp, self.slide_length, self.auto_length = radix2_exp, slide_length, auto_length
+        self.fft_length = 1 << radix2_exp
+        self.is_continue = False
+        fn = self._lib.pitchYINObj_new
+        fn.restype = c_int
+        fn.argtypes = [POINTER(c_void_p), POINTER(c_int), POINTER(c_float), POINTER(c_float), POINTER(c_int), POINTER(c_int),
+                       POINTER(c_int), POINTER(c_int)]
+        st = fn(ctypes.byref(self._obj), _util.opt_int(samplate), _util.opt_float(low_fre), _util.opt_float(high_fre),
+                _util.opt_int(radix2_exp), _util.opt_int(slide_length), _util.opt_int(auto_length), _util.opt_int(0))
+        if st != 0 or not self._obj:
+            self._obj = c_void_p(None)
+            raise RuntimeError(f"pitchYINObj_new failed with status {st}: {_lib.last_error()}")
+        for name in ("pitchYINObj_yinLength", "pitchYINObj_minIndex", "pitchYINObj_calTimeLength"):
+            getattr(self._lib, name).restype = c_int
+        self._lib.pitchYINObj_yinLength.argtypes = self._lib.pitchYINObj_minIndex.argtypes = [c_void_p]
+        self._lib.pitchYINObj_calTimeLength.argtypes = [c_void_p, c_int]
+        self.yin_length = int(self._lib.pitchYINObj_yinLength(self._obj))
+        self.min_index = int(self._lib.pitchYINObj_minIndex(self._obj))
+
+    def set_thresh(self, thresh):
+        """default 0.1; values <= 0 are ignored, as in the reference"""
+        fn = self._lib.pitchYINObj_setThresh
+        fn.restype, fn.argtypes = None, [c_void_p, c_float]
+        fn(self._obj, c_float(thresh))
+
+    def cal_time_length(self, data_length):
+        return int(self._lib.pitchYINObj_calTimeLength(self._obj, int(data_length)))
+
+    def pitch(self, data_arr):
+        """data_arr (..., n) -> fre_arr, value1_arr, value2_arr (..., time) float32: frequency of the first trough of the YIN
+        curve below the threshold (0 where there is none), the curve's value there, and the curve's minimum"""
+        x = _util.as_f32(data_arr)
+        if x.ndim < 1 or x.shape[-1] < 1:
+            raise ValueError("data_arr must have at least one sample")
+        n = x.shape[-1]
+        t = self.cal_time_length(n)
+        if x.ndim == 1:
+            fre, v1, v2 = (np.zeros(t, np.float32) for _ in range(3))
+            fn = _lib.checked(self._lib.pitchYINObj_pitch)
+            fn.restype = None
+            fn.argtypes = [c_void_p, _util.c_float_p, c_int, _util.c_float_p, _util.c_float_p, _util.c_float_p]
+            fn(self._obj, _util.fptr(x), n, _util.fptr(fre), _util.fptr(v1), _util.fptr(v2))
+            return fre, v1, v2
+        import torch
+        clips, lead = _util.flatten_leading(x, 1)
+        out = self.pitch_device(torch.from_numpy(np.ascontiguousarray(clips)).to("cuda"))
+        torch.cuda.current_stream().synchronize()
+        return tuple(_util.restore_leading(o.cpu().numpy(), lead) for o in out)
+
+    # -- additive: device-resident batches ----------------------------------
+    def _args(self, x, stream):
+        import torch
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+        s = stream if stream is not None else torch.cuda.current_stream(x.device)
+        return x.shape[0], x.shape[1], self.cal_time_length(x.shape[1]), s
+
+    def pitch_device(self, x, stream=None):
+        """x: CUDA/HIP torch.float32 (clips, n) -> (fre, value1, value2) torch (clips, time).  Every frame is written: fre and
+        value1 are 0 where no trough qualifies.  One launch, asynchronous on `stream` or torch's current stream."""
+        import torch
+        b, n, t, s = self._args(x, stream)
+        fre, v1, v2 = (torch.empty((b, t), dtype=torch.float32, device=x.device) for _ in range(3))
+        if t == 0:  # fewer samples than a frame
+            return fre, v1, v2
+        fn = self._lib.pitchYINObj_pitchBatchDevice
+        fn.restype = c_int
+        fn.argtypes = [c_void_p, c_void_p, c_int, c_int, c_longlong, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]
+        _lib.check(fn(self._obj, x.data_ptr(), b, n, x.stride(0), fre.data_ptr(), v1.data_ptr(), v2.data_ptr(), max(t, 1),
+                      s.cuda_stream), "pitchYINObj_pitchBatchDevice")
+        return fre, v1, v2
+
+    def troughs_device(self, x, max_troughs=4, stream=None):
+        """x: torch (clips, n) -> (fre, value, count): the first max_troughs troughs below the threshold per frame in lag order,
+        torch (clips, time, max_troughs) -- entries behind a frame's count are 0 --, and the count of ALL of them (clips, time) int32"""
+        import torch
+        b, n, t, s = self._args(x, stream)
+        with torch.cuda.stream(s):
+            fre = torch.zeros((b, t, max_troughs), dtype=torch.float32, device=x.device)
+            val = torch.zeros_like(fre)
+        cnt = torch.empty((b, t), dtype=torch.int32, device=x.device)
+        if t == 0:
+            return fre, val, cnt
+        fn = self._lib.pitchYINObj_troughsBatchDevice
+        fn.restype = c_int
+        fn.argtypes = [c_void_p, c_void_p, c_int, c_int, c_longlong, c_void_p, c_void_p, c_void_p, c_int, c_void_p]
+        _lib.check(fn(self._obj, x.data_ptr(), b, n, x.stride(0), fre.data_ptr(), val.data_ptr(), cnt.data_ptr(), int(max_troughs),
+                      s.cuda_stream), "pitchYINObj_troughsBatchDevice")
+        return fre, val, cnt
+
+    def curve_device(self, x, stream=None):
+        """x: torch (clips, n) -> the cumulative-mean-normalised difference curve, torch (clips, time, yin_length); column k is
+        lag min_index + k"""
+        import torch
+        b, n, t, s = self._args(x, stream)
+        out = torch.empty((b, t, self.yin_length), dtype=torch.float32, device=x.device)
+        if t == 0:
+            return out
+        fn = self._lib.pitchYINObj_curveBatchDevice
+        fn.restype = c_int
+        fn.argtypes = [c_void_p, c_void_p, c_int, c_int, c_longlong, c_void_p, c_void_p]
+        _lib.check(fn(self._obj, x.data_ptr(), b, n, x.stride(0), out.data_ptr(), s.cuda_stream), "pitchYINObj_curveBatchDevice")
+        return out
+
+    def __del__(self):
+        if getattr(self, "_obj", None):
+            fn = self._lib.pitchYINObj_free
+            fn.argtypes, fn.restype = [c_void_p], None
+            fn(self._obj)
+            self._obj = c_void_p(None)

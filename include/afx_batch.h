@@ -22,6 +22,7 @@
 #include "feature/spectral_algorithm.h"
 #include "feature/xxcc_algorithm.h"
 #include "mir/hpss_algorithm.h"
+#include "mir/_pitch_yin.h"
 #include "pwt_algorithm.h"
 #include "reassign_algorithm.h"
 #include "spectrogram_algorithm.h"
@@ -248,6 +249,27 @@ int hpssObj_spectraBatchDevice(HPSSObj hpssObj, const float *dData, int batch, i
  * AFX_ERR_UNSUPPORTED (-4): even order or order > 255; AFX_ERR_ARG: bad pointers / sizes / axis. */
 int afx_medianFilterDevice(const float *dIn, long long rows, int cols, int framesPerClip, int axis, int order, float *dOut,
                            void *hipStream);
+
+/* ---- YIN pitch contours of clips that already live in HBM (mir/_pitch_yin.h) -------------------------------------------
+ * batch clips of dataLength samples -> dFre / dTrough / dMin [b * outStride + t], t < pitchYINObj_calTimeLength(dataLength):
+ * frequency and curve value of the first trough below the threshold, and min of the curve.  Unlike pitchYINObj_pitch EVERY
+ * frame is written: dFre and dTrough are 0 where no trough qualifies (a found frequency is never 0).  dTrough / dMin may be
+ * NULL.  One launch on hipStream (NULL: the default stream), no scratch.  Objects created with isContinue = 1 return
+ * AFX_ERR_UNSUPPORTED (-4), the rule of the CQT calls above.  AFX_ERR_ARG (-6): NULL object / dData / dFre, batch <= 0, dataLength <= 0,
+ * clipStride < dataLength, outStride < frames.  Fewer samples than fftLength: nothing is written, 0 is returned. */
+int pitchYINObj_pitchBatchDevice(PitchYINObj pitchYINObj, const float *dData, int batch, int dataLength, long long clipStride,
+                                 float *dFre, float *dTrough, float *dMin, long long outStride, void *hipStream);
+/* every trough below the threshold, in lag order: dFre / dVal [(b * frames + t) * troughPitch + i] hold the first troughPitch
+ * candidates of a frame, dLen [b * frames + t] counts ALL of them (entries beyond min(dLen, troughPitch) are not written).
+ * The complete lists have yinLength / 2 + 1 columns -- gigabytes for a corpus --, hence the cap and the separate call. */
+int pitchYINObj_troughsBatchDevice(PitchYINObj pitchYINObj, const float *dData, int batch, int dataLength, long long clipStride,
+                                   float *dFre, float *dVal, int *dLen, int troughPitch, void *hipStream);
+/* the normalised difference curve itself: dYin [(b * frames + t) * yinLength + k], lag minIndex + k; pitchYINObj_yinLength
+ * gives yinLength, pitchYINObj_minIndex the first lag */
+int pitchYINObj_curveBatchDevice(PitchYINObj pitchYINObj, const float *dData, int batch, int dataLength, long long clipStride,
+                                 float *dYin, void *hipStream);
+int pitchYINObj_yinLength(PitchYINObj pitchYINObj);
+int pitchYINObj_minIndex(PitchYINObj pitchYINObj);
 
 #ifdef __cplusplus
 }
