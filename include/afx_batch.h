@@ -11,6 +11,15 @@
  * unless the caller switched streams).  Device variants are asynchronous on that stream; host variants
  * return with the result in host memory.  All return 0 or a negative status
  * (see afx_last_error()).
+ *
+ * The contract of every device call (enforced by tests/device_contract.py on the GPU and on the emulated kernels):
+ * of each input only the samples [b * stride, b * stride + length) are read into the result -- what lies in the stride
+ * gap, before the first or behind the last clip may be NaN or Inf; of each output only the documented words are written
+ * (no row-pitch padding, nothing behind the last row, nothing at all on a zero-frame call), and every documented word IS
+ * written; pointers need 4-byte alignment only (a 16-byte-aligned base and an even stride select the fastest kernels;
+ * for xxccObj_xxccDevice, stftObj_istftBatchDevice and spectralObj_computeDevice on rows of a multiple of 4 bins another
+ * alignment runs another instantiation whose results agree to the parity bar, 1e-5, instead of bit for bit); and the
+ * result of a call does not depend on the calls the object served before (scratch is reused, never trusted).
  */
 #ifndef AFX_BATCH_H
 #define AFX_BATCH_H

@@ -44,8 +44,15 @@ struct EmuIdx {
 };
 extern thread_local EmuIdx threadIdx, blockIdx, blockDim, gridDim;
 
+#ifdef AFX_EMU_VECTOR_TYPES
+// sanitizer builds (tests/test_device_contract_emulated.py): vector-extension types -- UBSan's alignment check covers their loads
+// and stores, which it does not for the copy of a plain aggregate, so a float4 access at a 4-byte-aligned address is a report
+typedef float float2 __attribute__((ext_vector_type(2)));
+typedef float float4 __attribute__((ext_vector_type(4)));
+#else
 struct alignas(8) float2 { float x, y; };
 struct alignas(16) float4 { float x, y, z, w; };
+#endif
 struct alignas(8) uint2 { unsigned x, y; };
 struct alignas(8) int2 { int x, y; };
 static inline float4 make_float4(float a, float b, float c, float d) { return float4{a, b, c, d}; }

@@ -216,3 +216,84 @@ def test_cepstrogram_wave_kernel(name):
             parity_log(f"{name} cepstrogram {nm} {stat} distance from float64", mine, bar, "max(TOL, 2 x the reference's)",
                        {"reference": theirs})
             assert mine <= bar, f"{name} {nm} {stat} vs float64: {mine:.3e} > {bar:.3e} (reference {theirs:.3e})"
+
+
+# ---- n_fft 256: the pair kernels (afx_stft256.hip, k_istft_w256) put two consecutive frames through ONE complex transform,
+# so a quiet frame shares its rounding with a loud neighbour.  The non-stationary clips at that size, and the bound stated in
+# DESIGN.md ("The device-pointer contract", last paragraph) for the worst pair: exact zeros next to full scale.
+PAIR_LEAK = 2e-7  # of the loud neighbour's peak (measured: 7.1e-8 forward, 6.3e-8 inverse)
+
+
+@pytest.mark.parametrize("hop", [64, 77])
+@pytest.mark.parametrize("name", cases.HARD_CLIPS)
+def test_stft_256_pair_kernel_on_non_stationary_clips(name, hop):
+    """k_stft_w256 through stft_device: COMPLEX and POWER against the compiled reference and float64, tensor and per-frame bars"""
+    import torch
+    x = clip(name)[:SR + 4096].astype(np.float32)  # the level step / the end of the silence sits at one second
+    rre, rim = ref.RefSTFT(8, 1, hop).stft(x)
+    f64 = restate.stft(x.astype(np.float64), 256, hop, 1)
+    o = af.STFT(radix2_exp=8, window_type=af.WindowType.HANN, slide_length=hop)
+    gre, gim = o.stft_device(torch.from_numpy(x[None]).cuda())
+    torch.cuda.synchronize()
+    got = (gre[0].cpu().numpy() + 1j * gim[0].cpu().numpy())[:, :129]
+    want = (rre + 1j * rim)[:, :129]
+    plain = name != "clicks"  # the file's per-frame bar everywhere but on the click train, where only the pair-aware bar below holds
+    check(f"stft256 complex {name} hop {hop}", got, want, f64, per_frame=plain)
+    check(f"stft256 power {name} hop {hop}", np.abs(got) ** 2, np.abs(want) ** 2, np.abs(f64) ** 2, per_frame=plain)
+    # per frame, pair-aware: 1e-5 of the frame's own peak + PAIR_LEAK of the louder neighbour's (the frame it may share a
+    # transform with).  The plain per-frame bar fails on "clicks" (measured: 3.8e-4 / 5.1e-4 of a -100 dB frame's peak next to
+    # a 0.9 click, i.e. 7e-8 of the click's): the pairing is kept, this is its documented bound.
+    pk = np.abs(f64).max(axis=1)
+    nb = np.maximum(np.r_[pk[1:], 0.0], np.r_[0.0, pk[:-1]])
+    for tag, other in (("float64", f64), ("reference", want)):
+        err = np.abs(got - other).max(axis=1)
+        over = err / (TOL * pk + PAIR_LEAK * np.maximum(nb, pk) + 1e-30)
+        parity_log(f"stft256 {name} hop {hop} per-frame (pair-aware) vs {tag}", float(over.max()) * TOL, TOL, "per-frame, pair-aware")
+        assert over.max() <= 1.0, f"stft256 {name} hop {hop} vs {tag}: frame {int(over.argmax())} is {over.max():.2f} x its pair-aware bar"
+
+
+@pytest.mark.parametrize("name", cases.HARD_CLIPS)
+def test_istft_256_pair_kernel_on_non_stationary_clips(name):
+    """k_istft_w256 through istft_device on the REFERENCE's spectrum: against the reference's inverse and float64"""
+    import torch
+    from tests.conftest import assert_istft_parity
+    x = clip(name)[SR - 4096:SR + 4096].astype(np.float32)
+    rr = ref.RefSTFT(8, 1, 64)
+    rre, rim = rr.stft(x)
+    w = restate.fft_window(1, 256)
+    f64 = restate.istft(rre.astype(np.float64) + 1j * rim, 256, 64, w)
+    o = af.STFT(radix2_exp=8, window_type=af.WindowType.HANN, slide_length=64)
+    y = o.istft_device(torch.from_numpy(rre[None]).cuda(), torch.from_numpy(rim[None]).cuda())[0].cpu().numpy()
+    gn = restate.istft_norm(rre.shape[0], 256, 64, w)
+    assert_istft_parity(y, f64, gn, f"istft256 {name} vs float64")
+    assert_istft_parity(y, rr.istft(rre, rim).astype(np.float64), gn, f"istft256 {name} vs reference")
+
+
+@pytest.mark.parametrize("frames", [4, 5])
+def test_pair_kernels_zero_frame_next_to_full_scale(frames):
+    """the worst pair: frames of exact zeros between full-scale frames (hop = n_fft: the frames do not overlap).  The
+    reference gives exact zeros; a frame that shares a transform with its neighbour gets that neighbour's float32 rounding.
+    Bound: PAIR_LEAK of the neighbour's peak, forward and inverse."""
+    import torch
+    rng = np.random.default_rng(256)
+    x = np.zeros(frames * 256, np.float32)
+    for t in range(0, frames, 2):
+        x[t * 256:(t + 1) * 256] = rng.uniform(-1.0, 1.0, 256)
+    o = af.STFT(radix2_exp=8, window_type=af.WindowType.RECT, slide_length=256)
+    gre, gim = o.stft_device(torch.from_numpy(x[None]).cuda())
+    torch.cuda.synchronize()
+    s = gre[0].cpu().numpy() + 1j * gim[0].cpu().numpy()
+    assert s.shape == (frames, 256) and np.isfinite(s).all()
+    loud = np.abs(s[0::2]).max()
+    leak = float(np.abs(s[1::2]).max() / loud)
+    parity_log(f"stft256 zero frame next to full scale, T {frames}", leak, PAIR_LEAK, "pair leakage / neighbour's peak")
+    assert leak <= PAIR_LEAK, f"forward: a silent frame holds {leak:.3e} of its neighbour's peak"
+    # inverse: the loud frames' spectra, exact zeros in between
+    sre, sim = gre.clone(), gim.clone()
+    sre[0, 1::2], sim[0, 1::2] = 0.0, 0.0
+    y = o.istft_device(sre, sim)[0].cpu().numpy().reshape(frames, 256)
+    leak_inv = float(np.abs(y[1::2]).max() / np.abs(y[0::2]).max())
+    parity_log(f"istft256 zero frame next to full scale, T {frames}", leak_inv, PAIR_LEAK, "pair leakage / neighbour's peak")
+    assert np.abs(y[0::2] - x.reshape(frames, 256)[0::2]).max() <= 1e-5 and leak_inv <= PAIR_LEAK, \
+        f"inverse: a silent frame holds {leak_inv:.3e} of its neighbour's peak"
+    print(f"n_fft 256 pair kernels, T {frames}: zero-frame leakage forward {leak:.3e}, inverse {leak_inv:.3e} of the neighbour's peak")
