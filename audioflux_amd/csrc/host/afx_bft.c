@@ -321,8 +321,7 @@ int afx_bft_create(const AfxBftPlan *p, BFTObj *bftObj) {
 
 int bftObj_calTimeLength(BFTObj o, int dataLength) {
     /* stftObj_calTimeLength without padding (src/stft_algorithm.c:225-262) */
-    if (!o || dataLength < o->fftLength) return 0;
-    return (dataLength - o->fftLength) / o->slideLength + 1;
+    return o ? afx_frames(dataLength, o->fftLength, o->slideLength) : 0;
 }
 
 float *bftObj_getFreBandArr(BFTObj o) { return o ? o->freBandArr : NULL; }
@@ -385,19 +384,8 @@ static int run_reassigned(BFTObj o, const float *dData, int batch, int dataLengt
         /* energy / rms / zcr come from the windowed frames, not from the spectrum: one STFT pass
          * whose bins are discarded (binCount 1) */
         AfxStftArgs a;
-        memset(&a, 0, sizeof(a));
-        a.x = dData;
-        a.clipStride = clipStride;
-        a.batch = batch;
-        a.dataLength = dataLength;
-        a.timeLength = T;
-        a.radix2Exp = o->radix2Exp;
-        a.hop = o->slideLength;
-        a.window = o->dWindow;
-        a.twiddle = o->dTwiddle;
-        a.mode = AFX_SPEC_POWER;
-        a.binCount = 1;
-        a.outRe = mRe;
+        afx_stft_args(&a, dData, clipStride, batch, dataLength, T, o->radix2Exp, o->slideLength, o->dWindow, o->dTwiddle,
+                      AFX_SPEC_POWER, 0, 1, mRe, NULL);
         a.energy = dTemporal;
         a.rms = dTemporal + frames;
         a.zcr = dTemporal + 2 * frames;
@@ -428,30 +416,19 @@ int afx_bft_run_device(BFTObj o, const float *dData, int batch, int dataLength,
                        void *stream) {
     const int T = bftObj_calTimeLength(o, dataLength);
     if (T <= 0 || batch <= 0) return AFX_OK;
-    /* scratch buffers belong to the object: drain the previous stream when the
-     * caller switches streams between calls */
-    if (o->lastStreamSet && o->lastStream != stream) {
-        int sst = afxdev_stream_sync(o->lastStream);
-        if (sst != AFX_OK) return sst;
-    }
-    o->lastStream = stream;
-    o->lastStreamSet = 1;
+    int st = afx_scratch_enter(&o->scratchStream, stream); /* dSpec, dOut, the fused plan's buffers */
+    if (st != AFX_OK) return st;
     int specMode, post;
     pick_modes(o, &specMode, &post);
     const int complexOut = !o->resultType;
     const int linear = (o->scale == SpectralFilterBankScale_Linear);
     const long long framesAll = (long long)batch * T;
 
+    /* what the size-generic forms below share -- all clips, every bin of the half spectrum; each sets its outputs, the
+     * linear form its bin slice, the dense form its chunk of clips */
     AfxStftArgs a;
-    memset(&a, 0, sizeof(a));
-    a.clipStride = clipStride;
-    a.dataLength = dataLength;
-    a.timeLength = T;
-    a.radix2Exp = o->radix2Exp;
-    a.hop = o->slideLength;
-    a.window = o->dWindow;
-    a.twiddle = o->dTwiddle;
-    a.mode = specMode;
+    afx_stft_args(&a, dData, clipStride, batch, dataLength, T, o->radix2Exp, o->slideLength, o->dWindow, o->dTwiddle, specMode, 0,
+                  o->F, NULL, NULL);
     a.normValue = o->normValue;
 
     if (o->reassign) return run_reassigned(o, dData, batch, dataLength, clipStride, dRe, dIm, dTemporal, stream);
@@ -464,8 +441,6 @@ int afx_bft_run_device(BFTObj o, const float *dData, int batch, int dataLength,
             afxdev_set_error("bft linear: %d bins for num=%d", count, o->num);
             return AFX_ERR_ARG;
         }
-        a.x = dData;
-        a.batch = batch;
         a.binLo = o->lowIndex;
         a.binCount = o->num;
         a.outRe = dRe;
@@ -482,16 +457,12 @@ int afx_bft_run_device(BFTObj o, const float *dData, int batch, int dataLength,
      * in the n_fft 2048 real-result kernel) */
     {
         int used = 0;
-        int st = afx_bft_try_fast(o, dData, batch, dataLength, clipStride, dRe, dIm, dTemporal, stream, &used);
+        st = afx_bft_try_fast(o, dData, batch, dataLength, clipStride, dRe, dIm, dTemporal, stream, &used);
         if (st != AFX_OK || used) return st;
     }
 
     /* banded bank: STFT and filter bank in one launch of the size-generic kernel */
     if (o->dBandMeta) {
-        a.x = dData;
-        a.batch = batch;
-        a.binLo = 0;
-        a.binCount = o->F;
         a.outRe = dRe;
         a.outIm = complexOut ? dIm : NULL;
         a.bandStart = o->dBandMeta;
@@ -518,7 +489,7 @@ int afx_bft_run_device(BFTObj o, const float *dData, int batch, int dataLength,
     long long chunk = (long long)(dense_chunk_bytes() / (perClip ? perClip : 1));
     if (chunk < 1) chunk = 1;
     if (chunk > batch) chunk = batch;
-    int st = afxdev_reserve((void **)&o->dSpec, &o->capSpec, perClip * (size_t)chunk);
+    st = afxdev_reserve((void **)&o->dSpec, &o->capSpec, perClip * (size_t)chunk);
     if (st != AFX_OK) return st;
 
     for (long long b0 = 0; b0 < batch; b0 += chunk) {
@@ -526,8 +497,6 @@ int afx_bft_run_device(BFTObj o, const float *dData, int batch, int dataLength,
         const long long frames = (long long)nb * T;
         a.x = dData + b0 * clipStride;
         a.batch = nb;
-        a.binLo = 0;
-        a.binCount = o->F;
         a.outPitch = pitch;
         a.outRe = o->dSpec;
         a.outIm = complexOut ? o->dSpec + frames * pitch : NULL;
@@ -611,10 +580,7 @@ void bftObj_bft(BFTObj o, float *dataArr, int dataLength, float *mRealArr3, floa
     }
     if (!dataArr || dataLength <= 0) return; /* stftObj_stft returns silently (stft_algorithm.c:267-269) */
     int st = bftObj_bftBatch(o, dataArr, 1, dataLength, mRealArr3, mImageArr3);
-    if (st != AFX_OK) {
-        o->status = st;
-        afxdev_report_failure("bftObj_bft", st);
-    }
+    if (st != AFX_OK) AFX_FAIL(o, st, "bftObj_bft");
 }
 
 void bftObj_getTemporalData(BFTObj o, float **eArr, float **rArr, float **zArr) {

@@ -104,15 +104,8 @@ int afx_bft_try_fast(struct OpaqueBFT *o, const float *dData, int batch, int dat
     if (st == AFX_ERR_UNSUPPORTED) return AFX_OK; /* size-generic kernels */
     if (st == AFX_OK && separate) {
         AfxStftArgs t;
-        memset(&t, 0, sizeof(t));
-        t.x = dData;
-        t.clipStride = clipStride;
-        t.batch = batch;
-        t.dataLength = dataLength;
-        t.timeLength = a.timeLength;
-        t.radix2Exp = o->radix2Exp;
-        t.hop = o->slideLength;
-        t.window = o->dWindow;
+        afx_stft_args(&t, dData, clipStride, batch, dataLength, a.timeLength, o->radix2Exp, o->slideLength, o->dWindow, NULL, 0, 0, 0,
+                      NULL, NULL);
         t.energy = dTemporal;
         t.rms = dTemporal + frames;
         t.zcr = dTemporal + 2 * frames;

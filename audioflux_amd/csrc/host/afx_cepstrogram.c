@@ -6,7 +6,9 @@
 #include <string.h>
 
 #include "afx_device.h"
+#include "afx_frametail.h"
 #include "afx_host.h"
+#include "afx_objkit.h"
 #include "cepstrogram_algorithm.h"
 
 struct OpaqueCepstrogram {
@@ -75,8 +77,7 @@ int cepstrogramObj_new(CepstrogramObj *cepstrogramObj, int radix2Exp, WindowType
 }
 
 int cepstrogramObj_calTimeLength(CepstrogramObj o, int dataLength) {
-    if (!o || dataLength < o->fftLength) return 0;
-    return (dataLength - o->fftLength) / o->slideLength + 1;
+    return o ? afx_frames(dataLength, o->fftLength, o->slideLength) : 0;
 }
 
 static void run(CepstrogramObj o, int cepNum, const float *hData, int dataLength, int T,
@@ -127,10 +128,7 @@ static void run(CepstrogramObj o, int cepNum, const float *hData, int dataLength
     if (st == AFX_OK && m3) st = afxdev_d2h(m3, a.out3, outB, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
     if (st == AFX_OK && hData) o->cachedTime = T;
-    if (st != AFX_OK) {
-        o->status = st;
-        afxdev_report_failure(who, st);
-    }
+    if (st != AFX_OK) AFX_FAIL(o, st, who);
 }
 
 /* clips already in HBM -> dOut1/2/3 [batch][T, N/2+1] left in HBM (include/afx_batch.h);
@@ -166,10 +164,7 @@ int cepstrogramObj_cepstrogramBatchDevice(CepstrogramObj o, int cepNum, const fl
     a.out2 = dOut2;
     a.out3 = dOut3;
     int st = afxk_cepstrogram(&a, hipStream);
-    if (st != AFX_OK) {
-        o->status = st;
-        afxdev_report_failure("cepstrogramObj_cepstrogramBatchDevice", st);
-    }
+    if (st != AFX_OK) AFX_FAIL(o, st, "cepstrogramObj_cepstrogramBatchDevice");
     return st;
 }
 

@@ -16,7 +16,9 @@
 #include <string.h>
 
 #include "afx_device.h"
+#include "afx_frametail.h"
 #include "afx_host.h"
+#include "afx_objkit.h"
 #include "cqt_algorithm.h"
 
 struct OpaqueCQT {
@@ -30,13 +32,7 @@ struct OpaqueCQT {
     float *sLenArr;          /* host, num: sqrt(len) */
     float taps[32];          /* resampler FIR h_j = table[256 j] */
     int timeLength;          /* frames of the last cqt call */
-    /* streaming (isContinue, cqt_algorithm.c:345-456): samples kept from the previous calls, and the assembled
-     * tail + new data of a call; tailLength < 0: that many samples of the next call are skipped (hop > fftLength) */
-    int isContinue;
-    float *tailData;         /* host, fftLength + slideLength floats */
-    int tailLength;
-    float *validData;        /* host */
-    size_t capValid;
+    AfxFrameTail tail;       /* streaming (isContinue, cqt_algorithm.c:345-456): the samples kept from the previous calls */
     /* device */
     void *stream;
     void *stream2;           /* side stream of the device call when the caller's stream IS `stream` */
@@ -62,8 +58,7 @@ struct OpaqueCQT {
     int pyrTiming;           /* -DAFX_EXPERIMENTS builds, AFX_CQT_PYR_TIMING set when the object was created */
     unsigned short *dDecTab; /* the resampler taps as the f16 table of k_cqt_pyramid (afx_cqt_dec_table) */
     unsigned long long *dTiming; /* AFX_CQT_PYR_TIMING=1: phase cycles of the instrumented kernel (afx_cqt_pyramid_timing) */
-    void *lastStream;        /* stream of the previous device call (scratch ordering) */
-    int lastUsed;
+    AfxScratchStream scratchStream; /* of the previous device call (scratch ordering) */
     float *dOut;             /* re | im [T,num] */
     size_t capOut;
     float *dIn;              /* chroma / cqcc staging */
@@ -73,11 +68,6 @@ struct OpaqueCQT {
     int devRadix;
     int status;
 };
-
-static void fail(CQTObj o, int st, const char *who) {
-    o->status = st;
-    afxdev_report_failure(who, st);
-}
 
 /* float32 -> IEEE binary16, round to nearest even (gcc 11 on x86-64 has no _Float16) */
 static unsigned short cqt_f32_to_f16(float f) {
@@ -262,7 +252,6 @@ int cqtObj_newWith(CQTObj *cqtObj, int num, int *samplate, float *minFre, int *b
     o->minFre = fmin;
     o->windowType = win;
     o->normType = norm;
-    o->isContinue = cont ? 1 : 0;
     {
         const char *e = getenv("AFX_CQT_PYRAMID"); /* read per object, at creation (no process-wide latch) */
         o->noPyramid = e && e[0] == '0';
@@ -298,20 +287,17 @@ int cqtObj_newWith(CQTObj *cqtObj, int num, int *samplate, float *minFre, int *b
     for (int i = 0; i < num; i++) o->sLenArr[i] = sqrtf(q * sr / (o->freBandArr[i] + bet / value));
     if (slide <= 0) slide = o->fftLength / 4;
     o->slideLength = slide;
-    if (o->isContinue) {
-        o->tailData = (float *)calloc((size_t)o->fftLength, sizeof(float));
-        if (!o->tailData) {
-            cqtObj_free(o);
-            free(lenTop);
-            return AFX_ERR_NOMEM;
-        }
-    }
     if (o->radix2Exp < 1 || o->radix2Exp > 14 || (slide >> (octaveNum - 1)) < 1) {
         afxdev_set_error("cqtObj_newWith: fftLength %d / slideLength %d unsupported for %d octaves",
                          o->fftLength, slide, octaveNum);
         cqtObj_free(o);
         free(lenTop);
         return AFX_ERR_UNSUPPORTED;
+    }
+    if (afx_frametail_init(&o->tail, o->fftLength, slide, cont) != AFX_OK) {
+        cqtObj_free(o);
+        free(lenTop);
+        return AFX_ERR_NOMEM;
     }
 
     /* ---- spectral kernels, thresholded, stored as bands */
@@ -476,54 +462,9 @@ int cqtObj_newWith(CQTObj *cqtObj, int num, int *samplate, float *minFre, int *b
 
 int cqtObj_calTimeLength(CQTObj o, int dataLength) {
     if (!o) return 0;
-    if (o->isContinue) { /* cqt_algorithm.c:281-288: whole frames of tail + new samples */
-        const long long total = (long long)dataLength + o->tailLength;
-        return total < o->fftLength ? 0 : (int)((total - o->fftLength) / o->slideLength + 1);
-    }
+    if (o->tail.isContinue) return afx_frametail_frames(&o->tail, dataLength); /* cqt_algorithm.c:281-288 */
     if (dataLength <= 0) return 0;
     return dataLength / o->slideLength + 1; /* padded framing, cqt_algorithm.c:289-297 */
-}
-
-/* Streaming object: the samples left over by the previous calls followed by the new ones, the frames they hold, and
- * the new tail (_cqtObj_dealData, cqt_algorithm.c:345-456; __calTimeAndTailLen :309-327).  Returns the number of
- * frames (0: not a whole frame yet -- everything went to the tail), < 0 on allocation failure; *valid / *validLength
- * = the assembled signal.  (A negative tail -- hop > fftLength -- is that many samples of the next call to skip.) */
-static int cqt_stream_take(CQTObj o, const float *data, int dataLength, const float **valid, int *validLength) {
-    const int N = o->fftLength, hop = o->slideLength;
-    const long long total = (long long)o->tailLength + dataLength;
-    *valid = NULL;
-    *validLength = 0;
-    if (total < N) {
-        if (total > 0) {
-            if (o->tailLength >= 0) memcpy(o->tailData + o->tailLength, data, sizeof(float) * (size_t)dataLength);
-            else memcpy(o->tailData, data - o->tailLength, sizeof(float) * (size_t)total);
-        }
-        o->tailLength = (int)total;
-        return 0;
-    }
-    const int frames = (int)((total - N) / hop + 1);
-    const int tailLen = (int)((total - N) % hop) + (N - hop);
-    if ((size_t)total + (size_t)N > o->capValid) {
-        float *p = (float *)realloc(o->validData, sizeof(float) * ((size_t)total + (size_t)N));
-        if (!p) return -1;
-        o->validData = p;
-        o->capValid = (size_t)total + (size_t)N;
-    }
-    int vl = 0;
-    if (o->tailLength < 0) {
-        vl = dataLength + o->tailLength;
-        memcpy(o->validData, data - o->tailLength, sizeof(float) * (size_t)vl);
-    } else {
-        if (o->tailLength > 0) memcpy(o->validData, o->tailData, sizeof(float) * (size_t)o->tailLength);
-        vl = o->tailLength;
-        memcpy(o->validData + vl, data, sizeof(float) * (size_t)dataLength);
-        vl += dataLength;
-    }
-    if (tailLen > 0) memcpy(o->tailData, o->validData + (vl - tailLen), sizeof(float) * (size_t)tailLen);
-    o->tailLength = tailLen;
-    *valid = o->validData;
-    *validLength = vl;
-    return frames;
 }
 
 int cqtObj_getFFTLength(CQTObj o) { return o ? o->fftLength : 0; }
@@ -538,7 +479,7 @@ void cqtObj_setScale(CQTObj o, int flag) {
  * padding.  AFX_CQT_PYRAMID=0 (read when the object is created) keeps the per-octave launches. */
 static int cqt_pyramid_ok(CQTObj o, int dataLength) {
     return !o->noPyramid && !afxdev_no_fused() && o->dTimeKernelH && o->dColMul && o->dDecTab && o->colTiles == 1 && o->radix2Exp == 9 &&
-           o->binPerOctave == 12 && o->octaveNum == AFX_CQT_PYR_LEVELS && o->slideLength == 128 && !o->isContinue &&
+           o->binPerOctave == 12 && o->octaveNum == AFX_CQT_PYR_LEVELS && o->slideLength == 128 && !o->tail.isContinue &&
            !o->vFlag && dataLength > 0 && dataLength <= (1 << 28) &&
            afxk_cqt_pyramid_plan(1, dataLength / 128 + 1, 0, NULL, NULL) > 0; /* (0: a device layer without the kernel) */
 }
@@ -606,7 +547,7 @@ int afx_cqt_pyramid_rings(CQTObj o, float *host, int wgs) {
     if (!o || !o->dRing || !host || wgs <= 0) return 0;
     const size_t bytes = sizeof(float) * (size_t)wgs * AFX_CQT_PYR_RING_FLOATS;
     if (bytes > o->capRing) return 0;
-    if (o->lastUsed) afxdev_stream_sync(o->lastStream);
+    afx_scratch_drain(&o->scratchStream);
     if (afxdev_d2h(host, o->dRing, bytes, o->stream) != AFX_OK || afxdev_stream_sync(o->stream) != AFX_OK) return 0;
     return wgs;
 }
@@ -616,7 +557,7 @@ int afx_cqt_pyramid_rings(CQTObj o, float *host, int wgs) {
 int afx_cqt_pyramid_timing(CQTObj o, unsigned long long *host) {
     if (!o || !o->dTiming || !host) return 0;
     const size_t bytes = sizeof(unsigned long long) * AFX_CQT_PYR_MAX_WGS * 11 * 8;
-    if (o->lastUsed) afxdev_stream_sync(o->lastStream);
+    afx_scratch_drain(&o->scratchStream);
     if (afxdev_d2h(host, o->dTiming, bytes, o->stream) != AFX_OK || afxdev_stream_sync(o->stream) != AFX_OK) return 0;
     afxdev_memset(o->dTiming, 0, bytes, o->stream);
     afxdev_stream_sync(o->stream);
@@ -629,7 +570,7 @@ int afx_cqt_pyramid_timing(CQTObj o, unsigned long long *host) {
 static int cqt_run_device(CQTObj o, const float *dX, int batch, int dataLength, long long xStride,
                           float *dRe, float *dIm, void *stream) {
     /* streaming objects frame from sample 0 (right padding) and keep whole frames only (cqt_algorithm.c:923-928) */
-    const int T = o->isContinue ? (dataLength - o->fftLength) / o->slideLength + 1 : dataLength / o->slideLength + 1;
+    const int T = o->tail.isContinue ? afx_frames(dataLength, o->fftLength, o->slideLength) : dataLength / o->slideLength + 1;
     const long long pitch = ((long long)dataLength / 2 + 3) & ~3LL;
     int st = AFX_OK;
     /* The decimation chain (signal of octave k from octave k+1: memory / latency bound) does not depend on
@@ -674,7 +615,7 @@ static int cqt_run_device(CQTObj o, const float *dX, int batch, int dataLength, 
     a.outIm = dIm;
     a.batch = batch;
     a.outStride = (long long)T * o->num;
-    a.rightPad = o->isContinue;
+    a.rightPad = o->tail.isContinue;
 
     const float *cur = dX;
     long long curStride = xStride;
@@ -729,39 +670,41 @@ void cqtObj_cqt(CQTObj o, float *dataArr, int dataLength, float *mRealArr, float
         return;
     }
     if (!dataArr || dataLength <= 0) return;
-    if (!o->isContinue && (!mRealArr || !mImageArr)) return;
-    const float *src = dataArr;
+    if (!o->tail.isContinue && (!mRealArr || !mImageArr)) return;
+    AfxFrameTake t = {0, 0, 0, dataLength}; /* not streaming: padded framing over the samples as they are */
     int T = dataLength / o->slideLength + 1;
-    if (o->isContinue) { /* tail of the previous calls + these samples; the rest waits for the next call */
-        T = cqt_stream_take(o, dataArr, dataLength, &src, &dataLength);
+    if (o->tail.isContinue) { /* [tail of the previous calls | these samples]; what follows the last frame waits for the next call */
+        const int noOutput = !mRealArr || !mImageArr;
+        T = afx_frametail_take(&o->tail, dataLength, &t);
         if (T < 0) {
-            fail(o, AFX_ERR_NOMEM, "cqtObj_cqt");
+            AFX_FAIL(o, T, "cqtObj_cqt");
             return;
         }
         o->timeLength = T;
-        if (T == 0) return; /* (the samples are kept; nothing is written) */
-        if (!mRealArr || !mImageArr) {
+        if (T == 0 || noOutput) afx_frametail_keep(&o->tail, dataArr, dataLength); /* the samples are taken in either way */
+        if (T == 0) return; /* (nothing is written) */
+        if (noOutput) {
             afxdev_set_error("cqtObj_cqt: %d frames are due but an output pointer is NULL", T);
-            fail(o, AFX_ERR_ARG, "cqtObj_cqt");
+            AFX_FAIL(o, AFX_ERR_ARG, "cqtObj_cqt");
             return;
         }
     }
+    const int n = t.total;
     const size_t outB = sizeof(float) * (size_t)T * o->num;
-    int st = AFX_OK;
-    if (o->lastUsed && o->lastStream != o->stream) st = afxdev_stream_sync(o->lastStream);
-    o->lastUsed = 0;
+    int st = afx_scratch_wait(&o->scratchStream, o->stream);
+    o->scratchStream.used = 0;
     if (st == AFX_OK) st = afxdev_reserve((void **)&o->dOut, &o->capOut, 2 * outB);
-    if (st == AFX_OK) st = afxdev_reserve((void **)&o->dX, &o->capX, sizeof(float) * (size_t)dataLength);
-    if (st == AFX_OK) st = afxdev_h2d(o->dX, src, sizeof(float) * (size_t)dataLength, o->stream);
+    if (st == AFX_OK) st = afx_frametail_upload(&o->tail, &t, dataArr, &o->dX, &o->capX, o->stream);
     float *dRe = o->dOut, *dIm = o->dOut + (size_t)T * o->num;
     if (st == AFX_OK)
-        st = cqt_pyramid_ok(o, dataLength) ? cqt_run_pyramid(o, o->dX, 1, dataLength, dataLength, dRe, dIm, NULL, 0, 0, o->stream)
-                                           : cqt_run_device(o, o->dX, 1, dataLength, dataLength, dRe, dIm, o->stream);
+        st = cqt_pyramid_ok(o, n) ? cqt_run_pyramid(o, o->dX, 1, n, n, dRe, dIm, NULL, 0, 0, o->stream)
+                                  : cqt_run_device(o, o->dX, 1, n, n, dRe, dIm, o->stream);
     if (st == AFX_OK) st = afxdev_d2h(mRealArr, dRe, outB, o->stream);
     if (st == AFX_OK) st = afxdev_d2h(mImageArr, dIm, outB, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
+    if (o->tail.isContinue) afx_frametail_keep(&o->tail, dataArr, dataLength);
     o->timeLength = T;
-    if (st != AFX_OK) fail(o, st, "cqtObj_cqt");
+    if (st != AFX_OK) AFX_FAIL(o, st, "cqtObj_cqt");
 }
 
 /* Clips per pass of the octave ladder.  Every octave kernel writes its 12 of the num columns of each output
@@ -791,7 +734,7 @@ static int cqt_chunk_clips(CQTObj o, int T, int batch) { return afx_cqt_pass_cli
 int cqtObj_cqtBatchDevice(CQTObj o, const float *dData, int batch, int dataLength,
                           long long clipStride, float *dReal, float *dImag, void *hipStream) {
     AFX_ENTER(o);
-    if (o && o->isContinue) { /* a streaming object carries one signal's tail from call to call */
+    if (o && o->tail.isContinue) { /* a streaming object carries one signal's tail from call to call */
         afxdev_set_error("cqtObj_cqtBatchDevice: the object was created with isContinue = 1; streaming objects take cqtObj_cqt");
         return AFX_ERR_UNSUPPORTED;
     }
@@ -802,7 +745,7 @@ int cqtObj_cqtBatchDevice(CQTObj o, const float *dData, int batch, int dataLengt
     int st = AFX_OK;
     const int T = dataLength / o->slideLength + 1;
     /* scratch is shared between calls: order this call after the previous one's stream */
-    if (o->lastStream != hipStream && o->lastUsed) st = afxdev_stream_sync(o->lastStream);
+    st = afx_scratch_wait(&o->scratchStream, hipStream);
     if (st == AFX_OK && cqt_pyramid_ok(o, dataLength)) { /* one launch for all clips: nothing to merge between passes */
         st = cqt_run_pyramid(o, dData, batch, dataLength, clipStride, dReal, dImag, NULL, 0, 0, hipStream);
     } else {
@@ -814,17 +757,16 @@ int cqtObj_cqtBatchDevice(CQTObj o, const float *dData, int batch, int dataLengt
                                 hipStream);
         }
     }
-    o->lastStream = hipStream;
-    o->lastUsed = 1;
+    afx_scratch_mark(&o->scratchStream, hipStream);
     o->timeLength = T;
-    if (st != AFX_OK) fail(o, st, "cqtObj_cqtBatchDevice");
+    if (st != AFX_OK) AFX_FAIL(o, st, "cqtObj_cqtBatchDevice");
     return st;
 }
 
 int cqtObj_cqtBatch(CQTObj o, const float *dataArr, int batch, int dataLength, float *mRealArr,
                     float *mImageArr) {
     AFX_ENTER(o);
-    if (o && o->isContinue) { /* a streaming object carries one signal's tail from call to call */
+    if (o && o->tail.isContinue) { /* a streaming object carries one signal's tail from call to call */
         afxdev_set_error("cqtObj_cqtBatch: the object was created with isContinue = 1; streaming objects take cqtObj_cqt");
         return AFX_ERR_UNSUPPORTED;
     }
@@ -843,7 +785,7 @@ int cqtObj_cqtBatch(CQTObj o, const float *dataArr, int batch, int dataLength, f
     if (st == AFX_OK) st = afxdev_d2h(mRealArr, dRe, outB, o->stream);
     if (st == AFX_OK) st = afxdev_d2h(mImageArr, dIm, outB, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
-    if (st != AFX_OK) fail(o, st, "cqtObj_cqtBatch");
+    if (st != AFX_OK) AFX_FAIL(o, st, "cqtObj_cqtBatch");
     return st;
 }
 
@@ -923,7 +865,7 @@ static int chroma_prepare(CQTObj o, int *chromaNum, SpectralDataType *dataType,
     if (cn != o->foldChromaNum) {
         unsigned char *fold = afx_chroma_fold(cn, o->num, o->binPerOctave, o->minFre);
         if (!fold) return AFX_ERR_NOMEM;
-        if (o->lastUsed) afxdev_stream_sync(o->lastStream); /* a launch may still read the old one */
+        afx_scratch_drain(&o->scratchStream); /* a launch may still read the old one */
         afxdev_free(o->dFold);
         o->dFold = NULL;
         st = afxdev_malloc((void **)&o->dFold, (size_t)cn * o->num);
@@ -966,7 +908,7 @@ void cqtObj_chroma(CQTObj o, int *chromaNum, SpectralDataType *dataType,
         st = afxk_cqt_chroma(dRe, dIm, T, o->num, o->dFold, o->haveLists ? &o->foldLists : NULL, cn, isMag, nrm, dC, o->stream);
     if (st == AFX_OK) st = afxdev_d2h(mDataArr, dC, sizeof(float) * (size_t)T * cn, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
-    if (st != AFX_OK) fail(o, st, "cqtObj_chroma");
+    if (st != AFX_OK) AFX_FAIL(o, st, "cqtObj_chroma");
 }
 
 /* chroma of `rows` = batch*T HBM-resident CQT frames (include/afx_batch.h) */
@@ -983,10 +925,9 @@ int cqtObj_chromaBatchDevice(CQTObj o, int *chromaNum, SpectralDataType *dataTyp
     if (st == AFX_OK)
         st = afxk_cqt_chroma(dReal, dImag, rows, o->num, o->dFold, o->haveLists ? &o->foldLists : NULL, cn, isMag, nrm, dData, hipStream);
     if (st == AFX_OK) {
-        o->lastStream = hipStream;
-        o->lastUsed = 1;
+        afx_scratch_mark(&o->scratchStream, hipStream);
     } else if (st != AFX_ERR_ARG) {
-        fail(o, st, "cqtObj_chromaBatchDevice");
+        AFX_FAIL(o, st, "cqtObj_chromaBatchDevice");
     }
     return st;
 }
@@ -997,7 +938,7 @@ int cqtObj_cqtChromaBatchDevice(CQTObj o, const float *dData, int batch, int dat
                                 float *dReal, float *dImag, int *chromaNum, SpectralDataType *dataType,
                                 ChromaDataNormalType *normType, float *dChroma, void *hipStream) {
     AFX_ENTER(o);
-    if (o && o->isContinue) { /* a streaming object carries one signal's tail from call to call */
+    if (o && o->tail.isContinue) { /* a streaming object carries one signal's tail from call to call */
         afxdev_set_error("cqtObj_cqtChromaBatchDevice: the object was created with isContinue = 1; streaming objects take cqtObj_cqt");
         return AFX_ERR_UNSUPPORTED;
     }
@@ -1009,7 +950,7 @@ int cqtObj_cqtChromaBatchDevice(CQTObj o, const float *dData, int batch, int dat
     int st = chroma_prepare(o, chromaNum, dataType, normType, &cn, &isMag, &nrm);
     if (st == AFX_ERR_ARG) return st;
     const int T = dataLength / o->slideLength + 1;
-    if (st == AFX_OK && o->lastStream != hipStream && o->lastUsed) st = afxdev_stream_sync(o->lastStream);
+    if (st == AFX_OK) st = afx_scratch_wait(&o->scratchStream, hipStream);
     if (st == AFX_OK && cqt_pyramid_ok(o, dataLength)) {
         /* 12 classes of 12 bins per octave: the sums travel with the rows through the one launch */
         const int fused = cn == 12 && o->haveLists;
@@ -1028,10 +969,9 @@ int cqtObj_cqtChromaBatchDevice(CQTObj o, const float *dData, int batch, int dat
                                      dChroma + (long long)b0 * T * cn, hipStream);
         }
     }
-    o->lastStream = hipStream;
-    o->lastUsed = 1;
+    afx_scratch_mark(&o->scratchStream, hipStream);
     o->timeLength = T;
-    if (st != AFX_OK) fail(o, st, "cqtObj_cqtChromaBatchDevice");
+    if (st != AFX_OK) AFX_FAIL(o, st, "cqtObj_cqtChromaBatchDevice");
     return st;
 }
 
@@ -1066,7 +1006,7 @@ void cqtObj_cqcc(CQTObj o, float *mDataArr1, int ccNum, CepstralRectifyType *rec
     }
     if (st == AFX_OK) st = afxdev_d2h(mDataArr2, dC, outB, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
-    if (st != AFX_OK) fail(o, st, "cqtObj_cqcc");
+    if (st != AFX_OK) AFX_FAIL(o, st, "cqtObj_cqcc");
 }
 
 /* transform length and twiddles of cqhc / deconv (_cqtObj_dealDeconv, cqt_algorithm.c:783-843) */
@@ -1112,7 +1052,7 @@ void cqtObj_cqhc(CQTObj o, float *mDataArr1, int hcNum, float *mDataArr2) {
     if (st == AFX_OK) st = afxdev_d2h(mDataArr2, dC, outB, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
     free(idx);
-    if (st != AFX_OK) fail(o, st, "cqtObj_cqhc");
+    if (st != AFX_OK) AFX_FAIL(o, st, "cqtObj_cqhc");
 }
 
 /* mDataArr1 [T,num] magnitudes -> mDataArr2 timbre (formant), mDataArr3 pitch, both [T,num] */
@@ -1134,7 +1074,7 @@ void cqtObj_deconv(CQTObj o, float *mDataArr1, float *mDataArr2, float *mDataArr
     if (st == AFX_OK) st = afxdev_d2h(mDataArr2, dT, inB, o->stream);
     if (st == AFX_OK) st = afxdev_d2h(mDataArr3, dP, inB, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
-    if (st != AFX_OK) fail(o, st, "cqtObj_deconv");
+    if (st != AFX_OK) AFX_FAIL(o, st, "cqtObj_deconv");
 }
 
 void cqtObj_free(CQTObj o) {
@@ -1166,7 +1106,6 @@ void cqtObj_free(CQTObj o) {
     afxdev_stream_destroy(o->stream);
     free(o->freBandArr);
     free(o->sLenArr);
-    free(o->tailData);
-    free(o->validData);
+    afx_frametail_free(&o->tail);
     free(o);
 }

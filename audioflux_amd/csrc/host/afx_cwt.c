@@ -14,6 +14,7 @@
 
 #include "afx_device.h"
 #include "afx_host.h"
+#include "afx_objkit.h"
 #include "cwt_algorithm.h"
 
 #ifndef M_E
@@ -53,8 +54,7 @@ struct OpaqueCWT {
     size_t capGA, capGXt, capGB;
     int haveSpectrum;
     int status;
-    void *lastStream;        /* stream of the previous batched device call (scratch ordering) */
-    int lastUsed;
+    AfxScratchStream scratchStream; /* of the previous batched device call (scratch ordering) */
 };
 
 /* ---- scale maps shared with the auditory bank (same formulas, see afx_auditory.c) ---- */
@@ -932,11 +932,8 @@ int *cwtObj_getBinBandArr(CWTObj o) { return o ? o->binBandArr : NULL; }
 
 static void run(CWTObj o, float *dataArr, const float *dBank, int isDet, float *re, float *im,
                 const char *who) {
-    int st = AFX_OK;
-    if (o->lastUsed && o->lastStream != o->stream) {
-        st = afxdev_stream_sync(o->lastStream);
-        o->lastUsed = 0;
-    }
+    int st = afx_scratch_wait(&o->scratchStream, o->stream);
+    if (o->scratchStream.stream != o->stream) o->scratchStream.used = 0; /* drained, or never used */
     const int small = o->dBankN != NULL; /* whole transform in LDS: natural-order spectrum in dXt */
     if (st == AFX_OK && dataArr) {
         st = afxdev_h2d(o->dX, dataArr, sizeof(float) * (size_t)o->dataLength, o->stream);
@@ -962,10 +959,7 @@ static void run(CWTObj o, float *dataArr, const float *dBank, int isDet, float *
     if (st == AFX_OK && re) st = afxdev_d2h(re, dRe, outB, o->stream);
     if (st == AFX_OK && im) st = afxdev_d2h(im, dIm, outB, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
-    if (st != AFX_OK) {
-        o->status = st;
-        afxdev_report_failure(who, st);
-    }
+    if (st != AFX_OK) AFX_FAIL(o, st, who);
 }
 
 void cwtObj_cwt(CWTObj o, float *dataArr, float *mRealArr3, float *mImageArr3) {
@@ -992,8 +986,7 @@ static int cwt_batch_device(CWTObj o, const float *dData, int chunks, long long 
         afxdev_set_error("%s: cwtObj_enableDet was not called", who);
         return AFX_ERR_ARG;
     }
-    int st = AFX_OK;
-    if (o->lastUsed && o->lastStream != hipStream) st = afxdev_stream_sync(o->lastStream);
+    int st = afx_scratch_wait(&o->scratchStream, hipStream);
     const size_t plane = (size_t)o->num * o->dataLength;
     const size_t L = (size_t)o->fftLength;
     if (st == AFX_OK && o->dBankN) {
@@ -1006,12 +999,8 @@ static int cwt_batch_device(CWTObj o, const float *dData, int chunks, long long 
                                 isDet ? o->dBankDetN : o->dBankN, o->num, isDet, o->dGXt, dReal + c * plane,
                                 dImag + c * plane, hipStream);
         }
-        o->lastStream = hipStream;
-        o->lastUsed = 1;
-        if (st != AFX_OK) {
-            o->status = st;
-            afxdev_report_failure(who, st);
-        }
+        afx_scratch_mark(&o->scratchStream, hipStream);
+        if (st != AFX_OK) AFX_FAIL(o, st, who);
         return st;
     }
     /* Forward transforms of up to 32 chunks share one launch (a single chunk is only
@@ -1111,13 +1100,9 @@ static int cwt_batch_device(CWTObj o, const float *dData, int chunks, long long 
         const int js = st == AFX_OK ? afxdev_stream_wait_stream(hipStream, tds) : afxdev_stream_sync(tds);
         if (st == AFX_OK) st = js;
     }
-    o->lastStream = hipStream;
-    o->lastUsed = 1;
+    afx_scratch_mark(&o->scratchStream, hipStream);
 
-    if (st != AFX_OK) {
-        o->status = st;
-        afxdev_report_failure(who, st);
-    }
+    if (st != AFX_OK) AFX_FAIL(o, st, who);
     return st;
 }
 
@@ -1205,7 +1190,7 @@ void cwtObj_free(CWTObj o) {
     if (o->stream2) afxdev_stream_sync(o->stream2);
     for (int i = 0; i < 3; i++)
         if (o->chain[i]) afxdev_stream_sync(o->chain[i]);
-    if (o->lastUsed && o->lastStream) afxdev_stream_sync(o->lastStream); /* the caller's stream may still run our kernels */
+    afx_scratch_drain(&o->scratchStream); /* the caller's stream may still run our kernels */
     afxdev_free(o->dTw);
     afxdev_free(o->dBankT);
     afxdev_free(o->dBankDetT);

@@ -155,8 +155,7 @@ void spectralObj_setEdgeArr(SpectralObj o, int *indexArr, int indexLength) {
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
     if (st != AFX_OK) {
         free(indexArr);
-        o->status = st;
-        afxdev_report_failure("spectralObj_setEdgeArr", st);
+        AFX_FAIL(o, st, "spectralObj_setEdgeArr");
         return;
     }
     free(o->indexArr);
@@ -261,10 +260,7 @@ static void run_host(SpectralObj o, const char *who, int timeLength, const float
     if (st == AFX_OK) st = afxdev_d2h(out0, o->dOut, sizeof(float) * T, o->stream);
     if (st == AFX_OK && two) st = afxdev_d2h(out1, o->dOut + T, sizeof(float) * T, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
-    if (st != AFX_OK) {
-        o->status = st;
-        afxdev_report_failure(who, st);
-    }
+    if (st != AFX_OK) AFX_FAIL(o, st, who);
 }
 
 static AfxSpectralRequest request(int kind, int i0, int i1, int i2, int i3, float f0) {

@@ -17,55 +17,53 @@ int afx_frametail_init(AfxFrameTail *f, int frameLength, int hop, int isContinue
 
 void afx_frametail_free(AfxFrameTail *f) {
     free(f->tail);
-    free(f->cur);
     memset(f, 0, sizeof(*f));
 }
 
 int afx_frametail_frames(const AfxFrameTail *f, int dataLength) {
-    long long total = dataLength;
-    if (f->isContinue) total += f->tailLength;
-    if (total < f->frameLength) return 0;
-    return (int)((total - f->frameLength) / f->hop + 1);
+    return afx_frames((long long)dataLength + (f->isContinue ? f->tailLength : 0), f->frameLength, f->hop);
 }
 
-int afx_frametail_push(AfxFrameTail *f, const float *data, int dataLength, int *curLength) {
-    const int N = f->frameLength, hop = f->hop;
+int afx_frametail_take(const AfxFrameTail *f, int dataLength, AfxFrameTake *t) {
     const int carried = f->isContinue ? f->tailLength : 0;
     const long long total = (long long)carried + dataLength;
-    *curLength = 0;
-    if (total < N) { /* no frame: the call extends the tail or works off the skip */
-        if (!f->isContinue) {
-            f->tailLength = 0;
-            return 0;
+    memset(t, 0, sizeof(*t));
+    if (total < f->frameLength) return 0; /* no frame: the call extends the tail or works off the skip */
+    if (total > 0x7fffffffLL) return AFX_ERR_ARG; /* (frames <= total) */
+    t->frames = afx_frames(total, f->frameLength, f->hop);
+    if (carried < 0) t->skip = -carried;
+    else t->head = carried;
+    t->total = (int)total;
+    return t->frames;
+}
+
+void afx_frametail_keep(AfxFrameTail *f, const float *data, int dataLength) {
+    const int N = f->frameLength, hop = f->hop, old = f->tailLength;
+    if (!f->isContinue) {
+        f->tailLength = 0;
+        return;
+    }
+    const long long total = (long long)old + dataLength;
+    /* without a frame everything stays; else what the last frame's hop leaves: < N, negative when the next frame starts
+     * beyond this call */
+    const long long left = total < N ? total : (total - N) % hop + (N - hop);
+    if (left > 0) { /* the last `left` samples of [tail | data] */
+        if (left <= dataLength) {
+            memcpy(f->tail, data + (dataLength - left), sizeof(float) * (size_t)left);
+        } else {
+            const size_t fromOld = (size_t)(left - dataLength); /* <= old */
+            memmove(f->tail, f->tail + ((size_t)old - fromOld), sizeof(float) * fromOld);
+            memcpy(f->tail + fromOld, data, sizeof(float) * (size_t)dataLength);
         }
-        if (total > 0) {
-            if (carried >= 0) memcpy(f->tail + carried, data, sizeof(float) * (size_t)dataLength);
-            else memcpy(f->tail, data - carried, sizeof(float) * (size_t)total);
-        }
-        f->tailLength = (int)total;
-        return 0;
     }
-    const long long frames = (total - N) / hop + 1;
-    const long long left = (total - N) % hop + (N - hop); /* < N; negative when the next frame starts beyond this call */
-    if (frames > 0x7fffffffLL || total > 0x7fffffffLL) return AFX_ERR_ARG;
-    if ((size_t)total > f->curCap) {
-        float *p = (float *)malloc(sizeof(float) * (size_t)total);
-        if (!p) return AFX_ERR_NOMEM;
-        free(f->cur);
-        f->cur = p;
-        f->curCap = (size_t)total;
-    }
-    if (carried < 0) {
-        memcpy(f->cur, data - carried, sizeof(float) * (size_t)total);
-    } else {
-        if (carried > 0) memcpy(f->cur, f->tail, sizeof(float) * (size_t)carried);
-        memcpy(f->cur + carried, data, sizeof(float) * (size_t)dataLength);
-    }
-    f->tailLength = 0;
-    if (f->isContinue) {
-        if (left > 0) memcpy(f->tail, f->cur + (total - left), sizeof(float) * (size_t)left);
-        f->tailLength = (int)left;
-    }
-    *curLength = (int)total;
-    return (int)frames;
+    f->tailLength = (int)left;
+}
+
+int afx_frametail_upload(const AfxFrameTail *f, const AfxFrameTake *t, const float *data, float **dX, size_t *capX,
+                         void *stream) {
+    const size_t head = (size_t)t->head, fresh = (size_t)t->total - head;
+    int st = afxdev_reserve((void **)dX, capX, sizeof(float) * (size_t)t->total);
+    if (st == AFX_OK && head > 0) st = afxdev_h2d(*dX, f->tail, sizeof(float) * head, stream);
+    if (st == AFX_OK && fresh > 0) st = afxdev_h2d(*dX + head, data + t->skip, sizeof(float) * fresh, stream);
+    return st;
 }

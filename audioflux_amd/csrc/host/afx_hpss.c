@@ -45,10 +45,6 @@ static int hpss_params(int radix2Exp, const WindowType *windowType, const int *h
     return 0;
 }
 
-static int frames_of(int dataLength, int fftLength, int hop) {
-    return dataLength < fftLength ? 0 : (dataLength - fftLength) / hop + 1;
-}
-
 int hpssObj_new(HPSSObj *hpssObj, int radix2Exp, WindowType *windowType, int *slideLength, int *hOrder, int *pOrder) {
     (void)slideLength; /* hpss_algorithm.c:81 overwrites it with fftLength/4 */
     if (!hpssObj) return -1;
@@ -83,30 +79,25 @@ int hpssObj_new(HPSSObj *hpssObj, int radix2Exp, WindowType *windowType, int *sl
 
 int hpssObj_calDataLength(HPSSObj o, int dataLength) {
     if (!o) return 0;
-    return (frames_of(dataLength, o->fftLength, o->slideLength) - 1) * o->slideLength + o->fftLength;
+    return (afx_frames(dataLength, o->fftLength, o->slideLength) - 1) * o->slideLength + o->fftLength;
 }
 
 /* chunks of whole clips: forward half spectrum -> masked spectra (or magnitudes) -> one inverse per requested output */
 static int run(HPSSObj o, const float *dData, int batch, int dataLength, long long clipStride, float *dH, float *dP,
                long long outStride, float *dHMag, float *dPMag, void *stream) {
     const int N = o->fftLength, F = N / 2 + 1, hop = o->slideLength;
-    const int T = frames_of(dataLength, N, hop);
+    const int T = afx_frames(dataLength, N, hop);
     if (T <= 0) return AFX_OK;
     const int nOut = (dH != NULL) + (dP != NULL);
-    /* the scratch belongs to the object: drain the previous stream on a switch */
-    if (o->lastStreamSet && o->lastStream != stream) {
-        int sst = afxdev_stream_sync(o->lastStream);
-        if (sst != AFX_OK) return sst;
-    }
-    o->lastStream = stream;
-    o->lastStreamSet = 1;
+    int st = afx_scratch_enter(&o->scratchStream, stream); /* dSpec */
+    if (st != AFX_OK) return st;
     const size_t clipFloats = (size_t)T * (2 * (size_t)F + 2 * (size_t)nOut * N);
     size_t chunk = chunk_bytes() / (sizeof(float) * clipFloats);
     if (chunk < 1) chunk = 1;
     if (chunk > (size_t)batch) chunk = (size_t)batch;
     /* (a launch of the transforms takes at most 2^31 - 1 frames) */
     while (chunk > 1 && chunk * (size_t)T > 0x7fffffffu) chunk /= 2;
-    int st = afxdev_reserve((void **)&o->dSpec, &o->capSpec, sizeof(float) * clipFloats * chunk);
+    st = afxdev_reserve((void **)&o->dSpec, &o->capSpec, sizeof(float) * clipFloats * chunk);
     if (st != AFX_OK) return st;
     for (int c0 = 0; c0 < batch; c0 += (int)chunk) {
         const int nc = batch - c0 < (int)chunk ? batch - c0 : (int)chunk;
@@ -115,21 +106,8 @@ static int run(HPSSObj o, const float *dData, int batch, int dataLength, long lo
         float *full = o->dSpec;
         float *sRe = full + 2 * (size_t)nOut * rows * N, *sIm = sRe + rows * F;
         AfxStftArgs s;
-        memset(&s, 0, sizeof(s));
-        s.x = dData + (long long)c0 * clipStride;
-        s.clipStride = clipStride;
-        s.batch = nc;
-        s.dataLength = dataLength;
-        s.timeLength = T;
-        s.radix2Exp = o->radix2Exp;
-        s.hop = hop;
-        s.window = o->stft->dWindow;
-        s.twiddle = o->stft->dTwiddle;
-        s.mode = AFX_SPEC_COMPLEX;
-        s.binLo = 0;
-        s.binCount = F;
-        s.outRe = sRe;
-        s.outIm = sIm;
+        afx_stft_args(&s, dData + (long long)c0 * clipStride, clipStride, nc, dataLength, T, o->radix2Exp, hop, o->stft->dWindow,
+                      o->stft->dTwiddle, AFX_SPEC_COMPLEX, 0, F, sRe, sIm);
         st = afxk_stft(&s, stream);
         if (st != AFX_OK) return st;
         AfxHpssArgs a;
@@ -169,7 +147,7 @@ int hpssObj_hpssBatchDevice(HPSSObj o, const float *dData, int batch, int dataLe
                             long long outStride, void *hipStream) {
     AFX_ENTER(o);
     if (!o || !dData || (!dH && !dP) || batch <= 0 || dataLength <= 0) return AFX_ERR_ARG;
-    if (frames_of(dataLength, o->fftLength, o->slideLength) > 0 && outStride < hpssObj_calDataLength(o, dataLength)) return AFX_ERR_ARG;
+    if (afx_frames(dataLength, o->fftLength, o->slideLength) > 0 && outStride < hpssObj_calDataLength(o, dataLength)) return AFX_ERR_ARG;
     return run(o, dData, batch, dataLength, clipStride, dH, dP, outStride, NULL, NULL, hipStream);
 }
 
@@ -199,7 +177,7 @@ void hpssObj_hpss(HPSSObj o, float *dataArr, int dataLength, float *hArr, float 
         return;
     }
     if ((!hArr && !pArr) || !dataArr || dataLength <= 0) return; /* hpss_algorithm.c:141-143 */
-    if (frames_of(dataLength, o->fftLength, o->slideLength) <= 0) return;
+    if (afx_frames(dataLength, o->fftLength, o->slideLength) <= 0) return;
     const int outLength = hpssObj_calDataLength(o, dataLength);
     const size_t inB = sizeof(float) * (size_t)dataLength, outB = sizeof(float) * (size_t)outLength;
     int st = afxdev_reserve((void **)&o->dX, &o->capX, inB);
@@ -214,10 +192,7 @@ void hpssObj_hpss(HPSSObj o, float *dataArr, int dataLength, float *hArr, float 
     if (st == AFX_OK && hArr) st = afxdev_d2h(hArr, o->dH, outB, o->stream);
     if (st == AFX_OK && pArr) st = afxdev_d2h(pArr, o->dP, outB, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
-    if (st != AFX_OK) {
-        o->status = st;
-        afxdev_report_failure("hpssObj_hpss", st);
-    }
+    if (st != AFX_OK) AFX_FAIL(o, st, "hpssObj_hpss");
 }
 
 void hpssObj_debug(HPSSObj o) {
@@ -229,7 +204,7 @@ void hpssObj_debug(HPSSObj o) {
 void hpssObj_free(HPSSObj o) {
     if (!o) return;
     if (o->stream) afxdev_stream_sync(o->stream);
-    if (o->lastStreamSet && o->lastStream != o->stream) afxdev_stream_sync(o->lastStream);
+    afx_scratch_drain(&o->scratchStream);
     afxdev_free(o->dSpec);
     afxdev_free(o->dX);
     afxdev_free(o->dH);
@@ -255,7 +230,7 @@ int afx_test_hpss_plan(int radix2Exp, const int *windowType, const int *slideLen
     if (st != 0) return st;
     const int N = 1 << radix2Exp, hop = N / 4;
     out[2] = hop;
-    out[5] = frames_of(dataLength, N, hop);
+    out[5] = afx_frames(dataLength, N, hop);
     out[6] = (out[5] - 1) * hop + N;
     return 0;
 }

@@ -5,6 +5,7 @@
 #include <stddef.h>
 
 #include "afx_frametail.h"
+#include "afx_objkit.h"
 #include "flux_base.h"
 #include "reassign_algorithm.h"
 
@@ -54,8 +55,7 @@ struct OpaqueBFT {
     int hTemporalCap, hTemporalFrames;
     int lastTimeLength;
     int status; /* last failure of a void entry point */
-    void *lastStream; /* stream of the previous launch (scratch is shared) */
-    int lastStreamSet;
+    AfxScratchStream scratchStream; /* stream of the previous launch (the scratch is shared; afx_objkit.h) */
 };
 
 struct OpaqueXXCC {
@@ -91,14 +91,13 @@ struct OpaqueSpectral {
 struct OpaqueSTFT {
     int fftLength, radix2Exp, slideLength;
     WindowType windowType;
-    int isContinue, isPad;
+    int isPad;
     PaddingPositionType positionType;
     PaddingModeType modeType;
     float padValue1, padValue2;
     float *windowDataArr; /* host [fftLength]; stftObj_useWindowDataArr overwrites it */
     int windowDirty;      /* dWindow is stale */
-    float *tailDataArr;   /* host [fftLength]: samples carried to the next streaming call */
-    int tailDataLength;   /* may be negative (hop > fftLength: samples still to skip) */
+    AfxFrameTail tail;    /* isContinue and the samples carried to the next streaming call; its hop follows slideLength */
     int timeLength;       /* frames of the last stft call */
     int methodType;       /* inverse: 0 weighted overlap-add, 1 overlap-add, -1 not built */
     float *winArr1, *winArr2; /* host: window^e, window^(e+1) */
@@ -106,8 +105,7 @@ struct OpaqueSTFT {
     float *dWindow, *dTwiddle, *dWin12;
     float *dX, *dOut, *dFrames; /* grow-only device scratch */
     size_t capX, capOut, capFrames;
-    void *lastStream;
-    int lastStreamSet;
+    AfxScratchStream scratchStream;
     int status;
 };
 
@@ -123,8 +121,8 @@ struct OpaqueReassign {
     float *dPlanes, *dX, *dOut; /* grow-only scratch */
     int *dIdx;
     size_t capPlanes, capIdx, capX, capOut;
-    void *lastStream;
-    int lastStreamSet, status;
+    AfxScratchStream scratchStream;
+    int status;
 };
 
 /* the harmonic / percussive separation object (afx_hpss.c, mir/hpss_algorithm.h) */
@@ -137,8 +135,7 @@ struct OpaqueHPSS {
     size_t capSpec;
     float *dX, *dH, *dP;     /* grow-only device buffers of the host-pointer call */
     size_t capX, capH, capP;
-    void *lastStream;        /* stream of the previous launch (the scratch is shared) */
-    int lastStreamSet;
+    AfxScratchStream scratchStream;
     int status;
 };
 
@@ -161,12 +158,6 @@ struct OpaquePitchYIN {
     size_t capHost;          /* frames the host arrays hold */
     int status;
 };
-
-/* framing state machine of a legacy stftObj_stft call, host fields of the object only
- * (afx_stft.c; also used by the spectrogram object for its isContinue mode) */
-int afx_stft_deal_data(struct OpaqueSTFT *o, const float *dataArr, int dataLength, int *valid,
-                       int *headTail, int *skip);
-void afx_stft_keep_tail(struct OpaqueSTFT *o, const float *dataArr, int dataLength, int total);
 
 /* validated parameters of a BFT execution plan (afx_bft.c) */
 typedef struct {

@@ -4,7 +4,7 @@
  * Mirrors the parameter semantics of the reference object (src/mir/_pitch_yin.c:87-196): defaults, clamps and the lag
  * range evaluated in float32.  Execution: ONE kernel launch per call (k_pitch_yin, afx_pitch_yin.hip) from the samples to
  * frequency / trough / min per frame, plus the candidate lists for the host-pointer call.  The host-pointer call is the
- * batch of one through staging buffers; it carries the isContinue tail (afx_frametail.c) and merges the result so that
+ * batch of one through staging buffers; it carries the isContinue tail (afx_frametail.h) and merges the result so that
  * frames without a trough keep the caller's freArr / valueArr1 entries.  There is no CPU compute path.
  */
 #include <math.h>
@@ -125,10 +125,6 @@ int pitchYINObj_calTimeLength(PitchYINObj o, int dataLength) {
 int pitchYINObj_yinLength(PitchYINObj o) { return o ? o->yinLength : 0; }
 int pitchYINObj_minIndex(PitchYINObj o) { return o ? o->minIndex : 0; }
 
-static int frames_of(const struct OpaquePitchYIN *o, int dataLength) {
-    return dataLength < o->fftLength ? 0 : (dataLength - o->fftLength) / o->slideLength + 1;
-}
-
 static void fill_args(const struct OpaquePitchYIN *o, const float *dData, int batch, int dataLength, long long clipStride, int T,
                       AfxPitchYinArgs *a) {
     memset(a, 0, sizeof(*a));
@@ -157,7 +153,7 @@ static int batch_enter(PitchYINObj o, const float *dData, int batch, int dataLen
     }
     int st = afxdev_bind_stream(hipStream);
     if (st != AFX_OK) return st;
-    *T = frames_of(o, dataLength);
+    *T = afx_frames(dataLength, o->fftLength, o->slideLength);
     return *T > 0;
 }
 
@@ -236,19 +232,25 @@ void pitchYINObj_pitch(PitchYINObj o, float *dataArr, int dataLength, float *fre
         return;
     }
     if (!dataArr || dataLength <= 0) return; /* _pitch_yin.c:234-236 */
-    int n = 0;
-    const int T = afx_frametail_push(&o->tail, dataArr, dataLength, &n);
-    int st = T < 0 ? T : AFX_OK;
+    AfxFrameTake t;
+    const int T = afx_frametail_take(&o->tail, dataLength, &t);
     o->timeLength = T > 0 ? T : 0;
-    if (T == 0) return;
-    if (st == AFX_OK && !freArr) st = AFX_ERR_ARG;
+    if (T < 0) {
+        AFX_FAIL(o, T, "pitchYINObj_pitch");
+        return;
+    }
+    if (T == 0) {
+        afx_frametail_keep(&o->tail, dataArr, dataLength);
+        return;
+    }
+    const int n = t.total;
+    int st = freArr ? AFX_OK : AFX_ERR_ARG;
     const int mLen = o->yinLength / 2 + 1;
-    const size_t rowB = sizeof(float) * (size_t)(T > 0 ? T : 0), candF = (size_t)(T > 0 ? T : 0) * (size_t)mLen;
+    const size_t rowB = sizeof(float) * (size_t)T, candF = (size_t)T * (size_t)mLen;
     if (st == AFX_OK) st = reserve_host(o, T);
-    if (st == AFX_OK) st = afxdev_reserve((void **)&o->dX, &o->capX, sizeof(float) * (size_t)n);
+    if (st == AFX_OK) st = afx_frametail_upload(&o->tail, &t, dataArr, &o->dX, &o->capX, o->stream);
     if (st == AFX_OK) st = afxdev_reserve((void **)&o->dOut, &o->capOut, 3 * rowB);
     if (st == AFX_OK) st = afxdev_reserve((void **)&o->dCand, &o->capCand, sizeof(float) * 2 * candF + sizeof(int) * (size_t)T);
-    if (st == AFX_OK) st = afxdev_h2d(o->dX, o->tail.cur, sizeof(float) * (size_t)n, o->stream);
     if (st == AFX_OK) {
         AfxPitchYinArgs a;
         fill_args(o, o->dX, 1, n, n, T, &a);
@@ -268,10 +270,10 @@ void pitchYINObj_pitch(PitchYINObj o, float *dataArr, int dataLength, float *fre
     if (st == AFX_OK) st = afxdev_d2h(o->mFreArr, o->dCand, sizeof(float) * candF, o->stream);
     if (st == AFX_OK) st = afxdev_d2h(o->mTroughArr, o->dCand + candF, sizeof(float) * candF, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
+    afx_frametail_keep(&o->tail, dataArr, dataLength); /* the samples are taken in whatever becomes of the frames */
     if (st != AFX_OK) {
-        o->status = st;
         o->timeLength = 0;
-        afxdev_report_failure("pitchYINObj_pitch", st);
+        AFX_FAIL(o, st, "pitchYINObj_pitch");
         return;
     }
     for (int i = 0; i < T; ++i) {
@@ -350,15 +352,17 @@ int afx_test_frametail(int frameLength, int hop, int isContinue, const float *da
     int st = afx_frametail_init(&f, frameLength, hop, isContinue);
     long long at = 0;
     for (int c = 0; st == AFX_OK && c < calls; ++c) {
-        int n = 0;
-        const int T = afx_frametail_push(&f, data + at, callLengths[c], &n);
+        const float *piece = data + at;
+        AfxFrameTake t;
+        const int T = afx_frametail_take(&f, callLengths[c], &t);
         if (T < 0) st = T;
         frames[c] = T;
-        tails[c] = f.tailLength;
-        curLengths[c] = n;
-        double s = 0.0;
-        for (int i = 0; i < n; ++i) s += (double)f.cur[i] * (double)(i + 1);
+        curLengths[c] = t.total;
+        double s = 0.0; /* over [tail head | piece past the skip], as the object uploads it */
+        for (int i = 0; i < t.total; ++i) s += (double)(i < t.head ? f.tail[i] : piece[t.skip + i - t.head]) * (double)(i + 1);
         sums[c] = s;
+        if (T >= 0) afx_frametail_keep(&f, piece, callLengths[c]);
+        tails[c] = f.tailLength;
         at += callLengths[c];
     }
     afx_frametail_free(&f);

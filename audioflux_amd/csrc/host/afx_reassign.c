@@ -82,8 +82,7 @@ int reassignObj_new(ReassignObj *reassignObj, int radix2Exp, int *samplate, Wind
 int reassignObj_calTimeLength(ReassignObj o, int dataLength) {
     if (!o) return 0;
     if (o->isPadding) return dataLength <= 0 ? 0 : dataLength / o->slideLength + 1;
-    if (dataLength < o->fftLength) return 0;
-    return (dataLength - o->fftLength) / o->slideLength + 1;
+    return afx_frames(dataLength, o->fftLength, o->slideLength);
 }
 
 void reassignObj_setResultType(ReassignObj o, int type) {
@@ -98,21 +97,8 @@ void reassignObj_setOrder(ReassignObj o, int order) {
 static int stft_planes(ReassignObj o, int which, const float *dData, int batch, int validLength,
                        long long clipStride, int T, float *dRe, float *dIm, void *stream) {
     AfxStftArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = dData;
-    a.clipStride = clipStride;
-    a.batch = batch;
-    a.dataLength = validLength;
-    a.timeLength = T;
-    a.radix2Exp = o->radix2Exp;
-    a.hop = o->slideLength;
-    a.window = o->dWin + (size_t)which * o->fftLength;
-    a.twiddle = o->dTwiddle;
-    a.mode = AFX_SPEC_COMPLEX;
-    a.binLo = 0;
-    a.binCount = o->F;
-    a.outRe = dRe;
-    a.outIm = dIm;
+    afx_stft_args(&a, dData, clipStride, batch, validLength, T, o->radix2Exp, o->slideLength, o->dWin + (size_t)which * o->fftLength,
+                  o->dTwiddle, AFX_SPEC_COMPLEX, 0, o->F, dRe, dIm);
     if (o->isPadding) a.padLeft = o->fftLength / 2; /* centre, zeros (stftObj_enablePadding default) */
     return afxk_stft(&a, stream);
 }
@@ -128,12 +114,8 @@ int reassignObj_reassignBatchDevice(ReassignObj o, const float *dData, int batch
     int valid = dataLength;
     if (o->isPadding && T > 1) valid = dataLength - dataLength % o->slideLength; /* tail dropped */
     const size_t plane = (size_t)batch * T * o->F;
-    if (o->lastStreamSet && o->lastStream != hipStream) {
-        int sst = afxdev_stream_sync(o->lastStream);
-        if (sst != AFX_OK) return sst;
-    }
-    o->lastStream = hipStream;
-    o->lastStreamSet = 1;
+    int st = afx_scratch_enter(&o->scratchStream, hipStream); /* dPlanes, dIdx */
+    if (st != AFX_OK) return st;
     if (o->resType == Reassign_None) {
         /* plain STFT, written (not accumulated) into the first pair (:226-249) */
         if (!dImag1) return AFX_ERR_ARG;
@@ -143,7 +125,7 @@ int reassignObj_reassignBatchDevice(ReassignObj o, const float *dData, int batch
     const int doTime = (o->resType == Reassign_Time || o->resType == Reassign_All);
     const int own = !(dReal2 && dImag2);
     /* scratch: [h re|im (when not handed out)] [dh re|im] [th re|im] + 2 (+1) index planes */
-    int st = afxdev_reserve((void **)&o->dPlanes, &o->capPlanes, sizeof(float) * plane * 6);
+    st = afxdev_reserve((void **)&o->dPlanes, &o->capPlanes, sizeof(float) * plane * 6);
     if (st == AFX_OK)
         st = afxdev_reserve((void **)&o->dIdx, &o->capIdx, sizeof(int) * plane * (o->order > 1 ? 3 : 2));
     if (st != AFX_OK) return st;
@@ -210,10 +192,7 @@ void reassignObj_reassign(ReassignObj o, float *dataArr, int dataLength, float *
     if (st == AFX_OK && wantS && mRealArr2) st = afxdev_d2h(mRealArr2, dS, pB, o->stream);
     if (st == AFX_OK && wantS && mImageArr2) st = afxdev_d2h(mImageArr2, dS + plane, pB, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
-    if (st != AFX_OK) {
-        o->status = st;
-        afxdev_report_failure("reassignObj_reassign", st);
-    }
+    if (st != AFX_OK) AFX_FAIL(o, st, "reassignObj_reassign");
 }
 
 void reassignObj_free(ReassignObj o) {

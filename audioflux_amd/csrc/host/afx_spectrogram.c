@@ -31,7 +31,7 @@ struct OpaqueSpectrogram {
     int baseNum;   /* chroma: bins in [lowIndex, highIndex]; log-chroma: rows of the base bank */
     float baseFre;
     WindowType windowType;
-    int slideLength, isContinue;
+    int slideLength;
     SpectralDataType dataType;
     SpectralFilterBankScaleType scale;
     SpectralFilterBankStyleType style;
@@ -46,7 +46,7 @@ struct OpaqueSpectrogram {
     BFTObj core;             /* STFT -> [coreRows] bank rows (or the linear bin slice) */
     int coreRows;
     float *dFold;            /* log-chroma: device [num, baseNum] 0/1 fold matrix */
-    struct OpaqueSTFT tail;  /* host-only: the streaming tail state machine (afx_stft.c) */
+    AfxFrameTail tail;       /* isContinue and the samples carried between spectrogram calls */
     XXCCObj xxcc;            /* lazily built cepstra plan over num bands */
     struct OpaqueSpectral *desc; /* lazily built descriptor object over num bands (afx_descriptor.c) */
     float *dDevTw;           /* deconv: twiddles of the 2^devRadix transform */
@@ -323,7 +323,6 @@ static int new_impl(SpectrogramObj *spectrogramObj, int num, int *samplate, floa
     o->baseFre = baseFre;
     o->windowType = win;
     o->slideLength = hop;
-    o->isContinue = cont;
     o->dataType = dtype;
     o->scale = scale;
     o->style = style;
@@ -331,11 +330,6 @@ static int new_impl(SpectrogramObj *spectrogramObj, int num, int *samplate, floa
     o->dataNormType = ChromaDataNormal_Max;
     o->normValue = 1;
     o->deepOrder = 1;
-    o->tail.radix2Exp = r;
-    o->tail.fftLength = fftLength;
-    o->tail.slideLength = hop;
-    o->tail.isContinue = cont;
-    o->tail.tailDataArr = (float *)calloc((size_t)fftLength, sizeof(float));
 
     /* --- the execution plan (spectrogram_algorithm.c:587-790) */
     const int F = fftLength / 2 + 1;
@@ -356,7 +350,7 @@ static int new_impl(SpectrogramObj *spectrogramObj, int num, int *samplate, floa
     p.style = style;
     p.normal = normal;
     float *chromaBank = NULL;
-    int st = o->tail.tailDataArr ? AFX_OK : AFX_ERR_NOMEM;
+    int st = afx_frametail_init(&o->tail, fftLength, hop, cont);
     const int bandLen = (is_chroma_like(scale) ? baseNum : num) + 2;
     o->freBandArr = (float *)calloc((size_t)bandLen, sizeof(float));
     o->binBandArr = (int *)calloc((size_t)bandLen, sizeof(int));
@@ -423,7 +417,7 @@ void spectrogramObj_setDataNormValue(SpectrogramObj o, float normValue) {
 }
 
 int spectrogramObj_calTimeLength(SpectrogramObj o, int dataLength) {
-    return o ? stftObj_calTimeLength(&o->tail, dataLength) : 0;
+    return o ? afx_frametail_frames(&o->tail, dataLength) : 0;
 }
 
 void spectrogramObj_enableDebug(SpectrogramObj o, int flag) {
@@ -435,11 +429,6 @@ float *spectrogramObj_getFreBandArr(SpectrogramObj o) { return o ? o->freBandArr
 int *spectrogramObj_getBinBandArr(SpectrogramObj o) { return o ? o->binBandArr : NULL; }
 int spectrogramObj_getBandNum(SpectrogramObj o) { return o ? o->num : 0; }
 int spectrogramObj_getBinBandLength(SpectrogramObj o) { return o ? o->num : 0; }
-
-static void fail(SpectrogramObj o, int st, const char *who) {
-    o->status = st;
-    afxdev_report_failure(who, st);
-}
 
 /* the norm exponent the core applies: for a magnitude chroma the reference raises the FOLDED
  * result (:1146-1152, :1196-1202), which k_row_post does; everything else is the BFT rule */
@@ -511,25 +500,24 @@ void spectrogramObj_spectrogram(SpectrogramObj o, float *dataArr, int dataLength
         return;
     }
     if (!dataArr || dataLength <= 0) return;
-    int valid = dataLength, headTail = 0, skip = 0, T;
-    o->tail.isContinue = o->isContinue;
-    if (o->isContinue) {
-        T = afx_stft_deal_data(&o->tail, dataArr, dataLength, &valid, &headTail, &skip);
-    } else {
-        T = stftObj_calTimeLength(&o->tail, dataLength);
+    AfxFrameTake t;
+    const int T = afx_frametail_take(&o->tail, dataLength, &t);
+    if (T < 0) {
+        AFX_FAIL(o, T, "spectrogramObj_spectrogram");
+        return;
     }
-    if (T <= 0) return; /* the reference keeps its previous frame count here as well */
+    if (T == 0) { /* the reference keeps its previous frame count here as well */
+        if (o->tail.isContinue) afx_frametail_keep(&o->tail, dataArr, dataLength);
+        return;
+    }
     o->timeLength = T;
     if (!mSpectArr) return;
-    const int upData = dataLength - skip, total = headTail + upData;
+    const int total = t.total;
     void *stream = o->core->stream;
     const size_t outB = sizeof(float) * (size_t)T * o->num;
     AFX_PHASE_T(0);
-    int st = afxdev_reserve((void **)&o->dX, &o->capX, sizeof(float) * (size_t)total);
-    if (st == AFX_OK) st = afxdev_reserve((void **)&o->dOut, &o->capOut, 2 * outB);
-    if (st == AFX_OK && headTail > 0)
-        st = afxdev_h2d(o->dX, o->tail.tailDataArr, sizeof(float) * (size_t)headTail, stream);
-    if (st == AFX_OK) st = afxdev_h2d(o->dX + headTail, dataArr + skip, sizeof(float) * (size_t)upData, stream);
+    int st = afxdev_reserve((void **)&o->dOut, &o->capOut, 2 * outB);
+    if (st == AFX_OK) st = afx_frametail_upload(&o->tail, &t, dataArr, &o->dX, &o->capX, stream);
     AFX_PHASE_T(1);
     if (st == AFX_OK) st = spectrogramObj_spectrogramBatchDevice(o, o->dX, 1, total, total, o->dOut, stream);
     AFX_PHASE_T(2);
@@ -538,27 +526,15 @@ void spectrogramObj_spectrogram(SpectrogramObj o, float *dataArr, int dataLength
     if (st == AFX_OK && mPhaseArr && o->scale == SpectralFilterBankScale_Linear) {
         /* phase of the sliced bins, real part clamped at 1e-16 (:1037-1053) */
         AfxStftArgs a;
-        memset(&a, 0, sizeof(a));
-        a.x = o->dX;
-        a.clipStride = total;
-        a.batch = 1;
-        a.dataLength = total;
-        a.timeLength = T;
-        a.radix2Exp = o->radix2Exp;
-        a.hop = o->slideLength;
-        a.window = o->core->dWindow;
-        a.twiddle = o->core->dTwiddle;
-        a.mode = AFX_SPEC_PHASE;
-        a.binLo = o->lowIndex;
-        a.binCount = o->num;
-        a.outRe = o->dOut + (size_t)T * o->num;
+        afx_stft_args(&a, o->dX, total, 1, total, T, o->radix2Exp, o->slideLength, o->core->dWindow, o->core->dTwiddle,
+                      AFX_SPEC_PHASE, o->lowIndex, o->num, o->dOut + (size_t)T * o->num, NULL);
         st = afxk_stft(&a, stream);
         if (st == AFX_OK) st = afxdev_d2h(mPhaseArr, a.outRe, outB, stream);
     }
     if (st == AFX_OK) st = afxdev_stream_sync(stream);
     AFX_PHASE_T(4);
-    if (o->isContinue) afx_stft_keep_tail(&o->tail, dataArr + skip, upData, total);
-    if (st != AFX_OK) fail(o, st, "spectrogramObj_spectrogram");
+    if (o->tail.isContinue) afx_frametail_keep(&o->tail, dataArr, dataLength);
+    if (st != AFX_OK) AFX_FAIL(o, st, "spectrogramObj_spectrogram");
 }
 
 void spectrogramObj_spectrogram1(SpectrogramObj o, float *mRealArr, float *mImageArr, int nLength,
@@ -611,7 +587,7 @@ void spectrogramObj_spectrogram1(SpectrogramObj o, float *mRealArr, float *mImag
     }
     if (st == AFX_OK) st = afxdev_d2h(mSpectArr, o->dOut, outB, stream);
     if (st == AFX_OK) st = afxdev_stream_sync(stream);
-    if (st != AFX_OK) fail(o, st, "spectrogramObj_spectrogram1");
+    if (st != AFX_OK) AFX_FAIL(o, st, "spectrogramObj_spectrogram1");
 }
 
 /* log10 / cube-root rectification + DCT-II, first ccNum coefficients (:1409-1475) */
@@ -622,7 +598,7 @@ static void run_xxcc(SpectrogramObj o, float *mDataArr1, int ccNum, CepstralRect
     if (!o->xxcc) {
         int st = xxccObj_new(&o->xxcc, o->num);
         if (st != 0) {
-            fail(o, st, who);
+            AFX_FAIL(o, st, who);
             return;
         }
     }
@@ -693,7 +669,7 @@ void spectrogramObj_deconv(SpectrogramObj o, float *mDataArr1, float *mDataArr2,
     if (st == AFX_OK) st = afxdev_d2h(mDataArr2, dT, inB, stream);
     if (st == AFX_OK) st = afxdev_d2h(mDataArr3, dP, inB, stream);
     if (st == AFX_OK) st = afxdev_stream_sync(stream);
-    if (st != AFX_OK) fail(o, st, "spectrogramObj_deconv");
+    if (st != AFX_OK) AFX_FAIL(o, st, "spectrogramObj_deconv");
 }
 
 /* ---- spectral descriptors: the object owns one descriptor state; the descriptor entry points themselves are in
@@ -708,7 +684,7 @@ struct OpaqueSpectral *afx_spectrogram_descriptor(SpectrogramObj o, const char *
         const int st = spectralObj_new(&o->desc, o->num, o->freBandArr);
         if (st != 0) {
             o->desc = NULL;
-            fail(o, st < -1 ? st : AFX_ERR_ARG, who);
+            AFX_FAIL(o, st < -1 ? st : AFX_ERR_ARG, who);
             return NULL;
         }
         /* spectrogram_algorithm.c:2648-2662: energy takes power rows as they are */
@@ -729,7 +705,7 @@ void spectrogramObj_preprocess(SpectrogramObj o, float *mDataArr1, float *mDataA
     float *dst = mDataArr3 ? mDataArr3 : mDataArr1;
     float *w = afx_window_fft(o->windowType, o->fftLength);
     if (!w) {
-        fail(o, AFX_ERR_NOMEM, "spectrogramObj_preprocess");
+        AFX_FAIL(o, AFX_ERR_NOMEM, "spectrogramObj_preprocess");
         return;
     }
     float value = 0;
@@ -744,7 +720,7 @@ void spectrogramObj_preprocess(SpectrogramObj o, float *mDataArr1, float *mDataA
     if (st == AFX_OK) st = afxk_desc_preprocess(o->dTmp, o->dTmp, o->timeLength, o->num, value, o->fftLength / 2, stream);
     if (st == AFX_OK) st = afxdev_d2h(dst, o->dTmp, bytes, stream);
     if (st == AFX_OK) st = afxdev_stream_sync(stream);
-    if (st != AFX_OK) fail(o, st, "spectrogramObj_preprocess");
+    if (st != AFX_OK) AFX_FAIL(o, st, "spectrogramObj_preprocess");
 }
 
 void spectrogramObj_free(SpectrogramObj o) {
@@ -759,7 +735,7 @@ void spectrogramObj_free(SpectrogramObj o) {
     xxccObj_free(o->xxcc);
     spectralObj_free(o->desc);
     bftObj_free(o->core);
-    free(o->tail.tailDataArr);
+    afx_frametail_free(&o->tail);
     free(o->freBandArr);
     free(o->binBandArr);
     free(o);

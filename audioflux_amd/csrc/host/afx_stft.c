@@ -38,18 +38,17 @@ int stftObj_new(STFTObj *stftObj, int radix2Exp, WindowType *windowType, int *sl
     o->slideLength = o->fftLength / 4 > 0 ? o->fftLength / 4 : 1; /* fftLength 2: the reference's default of 0 divides by
                                                                    * zero in its frame count (stft_algorithm.c:251) */
     if (slideLength && *slideLength > 0) o->slideLength = *slideLength;
-    o->isContinue = isContinue ? *isContinue : 0;
     o->positionType = PaddingPosition_Center;
     o->modeType = PaddingMode_Constant;
     o->methodType = -1;
 
     const size_t nb = sizeof(float) * (size_t)o->fftLength;
     o->windowDataArr = afx_window_fft(o->windowType, o->fftLength);
-    o->tailDataArr = (float *)calloc((size_t)o->fftLength, sizeof(float));
+    st = afx_frametail_init(&o->tail, o->fftLength, o->slideLength, isContinue ? *isContinue : 0);
     o->winArr1 = (float *)calloc((size_t)o->fftLength, sizeof(float));
     o->winArr2 = (float *)calloc((size_t)o->fftLength, sizeof(float));
     float *tw = afx_twiddle_table(o->fftLength);
-    if (!o->windowDataArr || !o->tailDataArr || !o->winArr1 || !o->winArr2 || !tw) st = AFX_ERR_NOMEM;
+    if (!o->windowDataArr || !o->winArr1 || !o->winArr2 || !tw) st = AFX_ERR_NOMEM;
     if (st == AFX_OK) st = afxdev_stream_create(&o->stream);
     if (st == AFX_OK) st = afxdev_malloc((void **)&o->dWindow, nb);
     if (st == AFX_OK) st = afxdev_malloc((void **)&o->dTwiddle, nb < 8 ? 8 : nb);
@@ -67,11 +66,11 @@ int stftObj_new(STFTObj *stftObj, int radix2Exp, WindowType *windowType, int *sl
 }
 
 void stftObj_setSlideLength(STFTObj o, int slideLength) {
-    if (o && slideLength > 0) o->slideLength = slideLength;
+    if (o && slideLength > 0) o->slideLength = o->tail.hop = slideLength;
 }
 
 void stftObj_enableContinue(STFTObj o, int flag) {
-    if (o) o->isContinue = flag;
+    if (o) o->tail.isContinue = flag != 0;
 }
 
 void stftObj_enablePadding(STFTObj o, int flag) {
@@ -96,25 +95,17 @@ void stftObj_useWindowDataArr(STFTObj o, float *winDataArr) {
 
 float *stftObj_getWindowDataArr(STFTObj o) { return o ? o->windowDataArr : NULL; }
 
-/* frames and dropped / kept tail of `dataLength` samples (stft_algorithm.c:826-850) */
-static void time_and_tail(int dataLength, int fftLength, int slideLength, int isPad, int *timeLen,
-                          int *tailLen) {
-    if (!isPad) {
-        *timeLen = (dataLength - fftLength) / slideLength + 1;
-        *tailLen = (dataLength - fftLength) % slideLength + (fftLength - slideLength);
-    } else {
-        *timeLen = dataLength / slideLength + 1;
-        *tailLen = (*timeLen > 1) ? dataLength % slideLength : 0;
-    }
+/* the padded framing (stft_algorithm.c:826-850): frames of `dataLength` samples; the ragged tail is dropped before
+ * padding (:650-653) and nothing is carried to the next call */
+static int padded_frames(int dataLength, int slideLength, int *valid) {
+    const int T = dataLength / slideLength + 1;
+    *valid = dataLength - (T > 1 ? dataLength % slideLength : 0);
+    return T;
 }
 
 int stftObj_calTimeLength(STFTObj o, int dataLength) {
     if (!o) return 0;
-    if (!o->isPad) {
-        if (o->isContinue) dataLength += o->tailDataLength;
-        if (dataLength < o->fftLength) return 0;
-        return (dataLength - o->fftLength) / o->slideLength + 1;
-    }
+    if (!o->isPad) return afx_frametail_frames(&o->tail, dataLength);
     if (dataLength <= 0) return 0;
     return dataLength / o->slideLength + 1;
 }
@@ -137,22 +128,9 @@ static int sync_window(STFTObj o, void *stream) {
  * timeLength frames; padding per the object's switches */
 static void fill_args(STFTObj o, AfxStftArgs *a, const float *dData, int batch, int validLength,
                       long long clipStride, int timeLength, float *dRe, float *dIm) {
-    memset(a, 0, sizeof(*a));
-    a->x = dData;
-    a->clipStride = clipStride;
-    a->batch = batch;
-    a->dataLength = validLength;
-    a->timeLength = timeLength;
-    a->radix2Exp = o->radix2Exp;
-    a->hop = o->slideLength;
-    a->window = o->dWindow;
-    a->twiddle = o->dTwiddle;
-    a->mode = AFX_SPEC_COMPLEX;
-    a->binLo = 0;
-    a->binCount = o->fftLength;
+    afx_stft_args(a, dData, clipStride, batch, validLength, timeLength, o->radix2Exp, o->slideLength, o->dWindow, o->dTwiddle,
+                  AFX_SPEC_COMPLEX, 0, o->fftLength, dRe, dIm);
     a->fullSpectrum = 1;
-    a->outRe = dRe;
-    a->outIm = dIm;
     if (!o->isPad) return;
     const int N = o->fftLength;
     /* where the data sits inside the padded clip (stft_algorithm.c:631-639) */
@@ -181,14 +159,8 @@ int stftObj_stftBatchDevice(STFTObj o, const float *dData, int batch, int dataLe
                             long long clipStride, float *dReal, float *dImag, void *hipStream) {
     AFX_ENTER(o);
     if (!o || !dData || !dReal || !dImag || batch <= 0 || dataLength <= 0) return AFX_ERR_ARG;
-    int T, tail, valid = dataLength;
-    if (o->isPad) {
-        time_and_tail(dataLength, o->fftLength, o->slideLength, 1, &T, &tail);
-        valid = dataLength - tail; /* the ragged tail is dropped before padding (:650-653) */
-    } else {
-        if (dataLength < o->fftLength) return AFX_OK;
-        T = (dataLength - o->fftLength) / o->slideLength + 1;
-    }
+    int valid = dataLength;
+    const int T = o->isPad ? padded_frames(dataLength, o->slideLength, &valid) : afx_frames(dataLength, o->fftLength, o->slideLength);
     if (T <= 0) return AFX_OK;
     int st = sync_window(o, hipStream);
     if (st != AFX_OK) return st;
@@ -197,70 +169,15 @@ int stftObj_stftBatchDevice(STFTObj o, const float *dData, int batch, int dataLe
     return afxk_stft(&a, hipStream);
 }
 
-/* streaming / padded framing state of one legacy call (stft_algorithm.c:474-599):
- * returns the frame count (0: nothing to transform), *total = samples to upload (tail + data),
- * *skip = leading samples of dataArr to drop (negative tail of a hop > fftLength stream) */
-int afx_stft_deal_data(STFTObj o, const float *dataArr, int dataLength, int *valid, int *headTail,
-                     int *skip) {
-    const int N = o->fftLength, H = o->slideLength;
-    int timeLen = 0, tailLen = 0;
-    *headTail = 0;
-    *skip = 0;
-    if (o->isPad) {
-        time_and_tail(dataLength, N, H, 1, &timeLen, &tailLen);
-        *valid = dataLength - tailLen;
-        o->tailDataLength = 0;
-        o->timeLength = timeLen;
-        return timeLen;
-    }
-    const int oldTail = o->isContinue ? o->tailDataLength : 0;
-    const int total = oldTail + dataLength;
-    if (total < N) {
-        /* not enough for one frame: keep everything for the next call (:498-501, :563-580) */
-        if (o->isContinue) {
-            if (total > 0) {
-                if (oldTail >= 0) memcpy(o->tailDataArr + oldTail, dataArr, sizeof(float) * (size_t)dataLength);
-                else memcpy(o->tailDataArr, dataArr - oldTail, sizeof(float) * (size_t)(dataLength + oldTail));
-            }
-            o->tailDataLength = total;
-        } else {
-            o->tailDataLength = 0;
-        }
-        o->timeLength = 0;
-        return 0;
-    }
-    time_and_tail(total, N, H, 0, &timeLen, &tailLen);
-    if (oldTail < 0) *skip = -oldTail;
-    else *headTail = oldTail;
-    *valid = total;
-    o->timeLength = timeLen;
-    return timeLen;
-}
-
-/* after the upload: the last tailLen samples of [old tail | data] become the new tail (:548-557) */
-void afx_stft_keep_tail(STFTObj o, const float *dataArr, int dataLength, int total) {
-    if (!o->isContinue || o->isPad) {
-        o->tailDataLength = 0;
-        return;
-    }
-    int timeLen, tailLen;
-    time_and_tail(total, o->fftLength, o->slideLength, 0, &timeLen, &tailLen);
-    if (tailLen > 0) {
-        if (tailLen <= dataLength) {
-            memcpy(o->tailDataArr, dataArr + (dataLength - tailLen), sizeof(float) * (size_t)tailLen);
-        } else {
-            const int fromOld = tailLen - dataLength; /* <= old tail length */
-            memmove(o->tailDataArr, o->tailDataArr + (o->tailDataLength - fromOld),
-                    sizeof(float) * (size_t)fromOld);
-            memcpy(o->tailDataArr + fromOld, dataArr, sizeof(float) * (size_t)dataLength);
-        }
-    }
-    o->tailDataLength = tailLen;
-}
-
-static void fail(STFTObj o, int st, const char *who) {
-    o->status = st;
-    afxdev_report_failure(who, st);
+/* framing of one legacy call (stft_algorithm.c:474-599): the frame count (0: nothing to transform, < 0: refused) and the
+ * signal to upload -- [kept tail | data past a skipped head] of a stream, the data without its ragged end in pad mode,
+ * which also forgets a carried tail */
+static int stft_take(STFTObj o, int dataLength, AfxFrameTake *t) {
+    if (!o->isPad) return afx_frametail_take(&o->tail, dataLength, t);
+    memset(t, 0, sizeof(*t));
+    t->frames = padded_frames(dataLength, o->slideLength, &t->total);
+    o->tail.tailLength = 0;
+    return t->frames;
 }
 
 void stftObj_stft(STFTObj o, float *dataArr, int dataLength, float *mRealArr, float *mImageArr) {
@@ -270,36 +187,31 @@ void stftObj_stft(STFTObj o, float *dataArr, int dataLength, float *mRealArr, fl
         return;
     }
     if (!dataArr || dataLength <= 0) return; /* stft_algorithm.c:267-269 */
-    int valid = dataLength, headTail = 0, skip = 0, T;
-    if (o->isPad || o->isContinue) {
-        T = afx_stft_deal_data(o, dataArr, dataLength, &valid, &headTail, &skip);
-    } else {
-        T = stftObj_calTimeLength(o, dataLength);
-        o->timeLength = T;
+    const int streaming = o->tail.isContinue && !o->isPad;
+    AfxFrameTake t;
+    const int T = stft_take(o, dataLength, &t);
+    if (T < 0) {
+        AFX_FAIL(o, T, "stftObj_stft");
+        return;
     }
-    if (T <= 0 || !mRealArr || !mImageArr) return;
+    o->timeLength = T;
+    if (T == 0 && streaming) afx_frametail_keep(&o->tail, dataArr, dataLength); /* all kept for the next call (:498-501, :563-580) */
+    if (T == 0 || !mRealArr || !mImageArr) return;
     const int N = o->fftLength;
     const size_t outB = sizeof(float) * (size_t)T * N;
-    /* device clip = [kept tail | data (minus a skipped head)]; in pad mode just the data */
-    const int upData = o->isPad ? valid : dataLength - skip;
-    const int total = headTail + upData;
-    int st = afxdev_reserve((void **)&o->dX, &o->capX, sizeof(float) * (size_t)(total > 0 ? total : 1));
-    if (st == AFX_OK) st = afxdev_reserve((void **)&o->dOut, &o->capOut, 2 * outB);
-    if (st == AFX_OK && headTail > 0)
-        st = afxdev_h2d(o->dX, o->tailDataArr, sizeof(float) * (size_t)headTail, o->stream);
-    if (st == AFX_OK && upData > 0)
-        st = afxdev_h2d(o->dX + headTail, dataArr + skip, sizeof(float) * (size_t)upData, o->stream);
+    int st = afxdev_reserve((void **)&o->dOut, &o->capOut, 2 * outB);
+    if (st == AFX_OK) st = afx_frametail_upload(&o->tail, &t, dataArr, &o->dX, &o->capX, o->stream);
     if (st == AFX_OK) st = sync_window(o, o->stream);
     if (st == AFX_OK) {
         AfxStftArgs a;
-        fill_args(o, &a, o->dX, 1, o->isPad ? valid : total, total, T, o->dOut, o->dOut + (size_t)T * N);
+        fill_args(o, &a, o->dX, 1, t.total, t.total, T, o->dOut, o->dOut + (size_t)T * N);
         st = afxk_stft(&a, o->stream);
     }
     if (st == AFX_OK) st = afxdev_d2h(mRealArr, o->dOut, outB, o->stream);
     if (st == AFX_OK) st = afxdev_d2h(mImageArr, o->dOut + (size_t)T * N, outB, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
-    if (o->isContinue && !o->isPad) afx_stft_keep_tail(o, dataArr + skip, dataLength - skip, total);
-    if (st != AFX_OK) fail(o, st, "stftObj_stft");
+    if (streaming) afx_frametail_keep(&o->tail, dataArr, dataLength); /* after the upload (:548-557) */
+    if (st != AFX_OK) AFX_FAIL(o, st, "stftObj_stft");
 }
 
 /* synthesis windows w^e and w^(e+1) (stft_algorithm.c:333-372), uploaded when they change */
@@ -323,14 +235,8 @@ int stftObj_istftBatchDevice(STFTObj o, const float *dReal, const float *dImag, 
                              void *hipStream) {
     AFX_ENTER(o);
     if (!o || !dReal || !dImag || !dData || batch <= 0 || nLength <= 0) return AFX_ERR_ARG;
-    /* the frame scratch belongs to the object: drain the previous stream on a switch */
-    if (o->lastStreamSet && o->lastStream != hipStream) {
-        int sst = afxdev_stream_sync(o->lastStream);
-        if (sst != AFX_OK) return sst;
-    }
-    o->lastStream = hipStream;
-    o->lastStreamSet = 1;
-    int st = sync_synthesis(o, type, hipStream);
+    int st = afx_scratch_enter(&o->scratchStream, hipStream); /* dFrames */
+    if (st == AFX_OK) st = sync_synthesis(o, type, hipStream);
     if (st != AFX_OK) return st;
     AfxIstftArgs a;
     memset(&a, 0, sizeof(a));
@@ -379,7 +285,7 @@ void stftObj_istft(STFTObj o, float *mRealArr, float *mImageArr, int nLength, in
                                       o->dX, dataLength, o->stream);
     if (st == AFX_OK) st = afxdev_d2h(dataArr, o->dX, dataB, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
-    if (st != AFX_OK) fail(o, st, "stftObj_istft");
+    if (st != AFX_OK) AFX_FAIL(o, st, "stftObj_istft");
 }
 
 void stftObj_debug(STFTObj o) {
@@ -399,7 +305,7 @@ void stftObj_free(STFTObj o) {
     afxdev_free(o->dFrames);
     afxdev_stream_destroy(o->stream);
     free(o->windowDataArr);
-    free(o->tailDataArr);
+    afx_frametail_free(&o->tail);
     free(o->winArr1);
     free(o->winArr2);
     free(o);
@@ -420,33 +326,27 @@ int afx_test_stft_stream(int radix2Exp, int slideLength, int isPad, const float 
     s.radix2Exp = radix2Exp;
     s.fftLength = 1 << radix2Exp;
     s.slideLength = slideLength;
-    s.isContinue = 1;
     s.isPad = isPad;
-    s.tailDataArr = (float *)calloc((size_t)s.fftLength, sizeof(float));
-    if (!s.tailDataArr) return AFX_ERR_NOMEM;
+    int st = afx_frametail_init(&s.tail, s.fftLength, slideLength, 1);
     long long off = 0, w = 0;
-    for (int c = 0; c < calls; c++) {
+    for (int c = 0; st == AFX_OK && c < calls; c++) {
         const float *chunk = data + off;
         const int n = chunkLens[c];
-        int valid = n, headTail = 0, skip = 0;
-        if (stftObj_calTimeLength(&s, n) < 0) {
-            free(s.tailDataArr);
-            return AFX_ERR_ARG;
+        AfxFrameTake t;
+        const int T = stft_take(&s, n, &t);
+        if (T < 0) {
+            st = T;
+            break;
         }
-        const int T = afx_stft_deal_data(&s, chunk, n, &valid, &headTail, &skip);
         timeLens[c] = T;
-        curLens[c] = 0;
-        if (T > 0) {
-            const int upData = s.isPad ? valid : n - skip;
-            memcpy(cur + w, s.tailDataArr, sizeof(float) * (size_t)headTail);
-            memcpy(cur + w + headTail, chunk + skip, sizeof(float) * (size_t)upData);
-            curLens[c] = headTail + upData;
-            w += curLens[c];
-            if (!s.isPad) afx_stft_keep_tail(&s, chunk + skip, n - skip, headTail + upData);
-        }
-        tails[c] = s.tailDataLength;
+        curLens[c] = t.total;
+        memcpy(cur + w, s.tail.tail, sizeof(float) * (size_t)t.head);
+        memcpy(cur + w + t.head, chunk + t.skip, sizeof(float) * (size_t)(t.total - t.head));
+        w += t.total;
+        if (!s.isPad) afx_frametail_keep(&s.tail, chunk, n);
+        tails[c] = s.tail.tailLength;
         off += n;
     }
-    free(s.tailDataArr);
-    return AFX_OK;
+    afx_frametail_free(&s.tail);
+    return st;
 }

@@ -7,6 +7,7 @@
 
 #include "afx_device.h"
 #include "afx_host.h"
+#include "afx_objkit.h"
 #include "synsq_algorithm.h"
 
 struct OpaqueSynsq {
@@ -96,10 +97,7 @@ void synsqObj_synsq(SynsqObj o, float *freArr, SpectralFilterBankScaleType scale
     if (st == AFX_OK) st = afxdev_d2h(mImageArr2, dOi, pB, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
     free(fn);
-    if (st != AFX_OK) {
-        o->status = st;
-        afxdev_report_failure("synsqObj_synsq", st);
-    }
+    if (st != AFX_OK) AFX_FAIL(o, st, "synsqObj_synsq");
 }
 
 void synsqObj_free(SynsqObj o) {

@@ -11,6 +11,7 @@
 #include "afx_batch.h"
 #include "afx_device.h"
 #include "afx_host.h"
+#include "afx_objkit.h"
 #include "wsst_algorithm.h"
 
 struct OpaqueWSST {
@@ -150,10 +151,7 @@ void wsstObj_wsst(WSSTObj o, float *dataArr, float *mRealArr1, float *mImageArr1
     if (st == AFX_OK && mRealArr2) st = afxdev_d2h(mRealArr2, dC, pB, o->stream);
     if (st == AFX_OK && mImageArr2) st = afxdev_d2h(mImageArr2, dC + plane, pB, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
-    if (st != AFX_OK) {
-        o->status = st;
-        afxdev_report_failure("wsstObj_wsst", st);
-    }
+    if (st != AFX_OK) AFX_FAIL(o, st, "wsstObj_wsst");
 }
 
 void wsstObj_free(WSSTObj o) {

@@ -94,10 +94,7 @@ void xxccObj_xxcc(XXCCObj o, float *mDataArr1, int ccNum, CepstralRectifyType *r
     if (st == AFX_OK)
         st = afxdev_d2h(mDataArr2, o->dOut, sizeof(float) * (size_t)o->timeLength * ccNum, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
-    if (st != AFX_OK) {
-        o->status = st;
-        afxdev_report_failure("xxccObj_xxcc", st);
-    }
+    if (st != AFX_OK) AFX_FAIL(o, st, "xxccObj_xxcc");
 }
 
 /* host pointers, explicit row count: mDataArr1[rows,num] -> mDataArr2[rows,ccNum]; the same
@@ -116,10 +113,7 @@ int xxccObj_xxccBatch(XXCCObj o, const float *mDataArr1, long long rows, int ccN
         st = afxdev_d2h(mDataArr2, o->dOut, sizeof(float) * (size_t)rows * ccNum, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
     o->timeLength = keep;
-    if (st != AFX_OK) {
-        o->status = st;
-        afxdev_report_failure("xxccObj_xxccBatch", st);
-    }
+    if (st != AFX_OK) AFX_FAIL(o, st, "xxccObj_xxccBatch");
     return st;
 }
 
@@ -159,10 +153,7 @@ void xxccObj_xxccStandard(XXCCObj o, float *mDataArr1, int ccNum, float *energyA
     if (st == AFX_OK && mDeltaArr1) st = afxdev_d2h(mDeltaArr1, dD1, outBytes, o->stream);
     if (st == AFX_OK && mDeltaArr2) st = afxdev_d2h(mDeltaArr2, dD2, outBytes, o->stream);
     if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
-    if (st != AFX_OK) {
-        o->status = st;
-        afxdev_report_failure("xxccObj_xxccStandard", st);
-    }
+    if (st != AFX_OK) AFX_FAIL(o, st, "xxccObj_xxccStandard");
 }
 
 void xxccObj_free(XXCCObj o) {
