@@ -5,9 +5,15 @@ driver records), plus the two other measured configurations of BASELINE.json in 
 shape: --config 4 (CWT morlet, 84 scales, 1000 x 10 s @ 44.1 kHz) and --config 5 (CQT 84 bins +
 chroma, 30 s @ 44.1 kHz clips, 125 clips per GPU).
 
-    python bench.py --gpus 1 --steps K --warmup W [--config 2|4|5] [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps K --warmup W [--config 2|4|5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what its headline figure needs and nothing else: it builds the inputs, warms up, times the K steps,
+writes --dump-outputs and prints the line.  --full adds every other leg described below, each after the timed region
+(`sustained_ms` and the clock probe, the oracle check, `cpu_baseline`, `secondary`, `dense_bank`, `legacy`, the device's
+power cap and temperature); its --no-* switches take single legs out again and mean nothing without it.  The line says
+which of the two it was (`full`); what a plain run did not measure is null or absent.
 
 A "step" is one pass of the hot path over one batch per GPU, inputs already resident in HBM,
 features left in HBM; with N > 1 each rank owns its own batch (weak scaling: clips are independent,
@@ -19,22 +25,22 @@ prints ONE JSON line.
 `roofline`: cfg 2 is ONE kernel launch per step (k_stft_mel_v2: STFT -> |S|^2 -> mel bank -> log10 ->
 DCT-II); it is timed live with HIP events on the stream it is launched on (torch's current stream is
 handed to the library).  `achieved` = SURVEY 8d's algorithmic bytes per unit x units per launch /
-that duration; `sustained_ms` repeats the step back to back for >= 1 s (sustained clocks, where the
+that duration; `sustained_ms` (--full) repeats the step back to back for >= 1 s (sustained clocks, where the
 K-step region of a short run sees boost clocks); `traffic` = HBM bytes per launch from the round's
 own rocprofv3 --pmc passes of this command (profiles/r06_bench_cfg<N>_pmc.json, written by
-tools/prof_traffic.py), null when that file is absent.  After the timed region clip 0 of the
+tools/prof_traffic.py), null when that file is absent.  With --full, after the timed region clip 0 of the
 benchmarked outputs is checked against the oracle (1e-5 peak / L2).
-`secondary` (--config 2 at one GPU, the driver's line): cfg 4 and cfg 5 measured in the same process after the
+`secondary` (--full --config 2 at one GPU): cfg 4 and cfg 5 measured in the same process after the
 headline -- value, ms_per_step, frac, PMC traffic, oracle check each.  With N > 1 `gather` says whether the
 exchange hides behind the compute: gather_ms (device time of the collective on rank 0's side stream),
 exposed_ms (step time beyond the step's own compute) and overlap_hidden_ms.
-`dense_bank` (same line): the dense filter-bank route north_star names as the MFMA path -- gammatone-128 at the headline shape as
+`dense_bank` (same runs): the dense filter-bank route north_star names as the MFMA path -- gammatone-128 at the headline shape as
 frames/s with its own oracle check, and the route's product alone (k_gemm_bank_bf16x3, one chunk's shape) as bf16 matrix FLOP/s
 against the 2.5 PF/s dense peak (`roofline.bound` "mfma"); mfma_busy is replayed from profiles/r06_rocprofv3_dense.txt.
 --dump-outputs DIR: once the K timed steps are fenced, what step K - 1 left for the caller goes to DIR/<name>.npy in float32 (cfg 2: mel,
 mfcc; cfg 4: cwt_real, cwt_imag of the step's last call; cfg 5: cqt_real, cqt_imag, chroma), at most 64 MB in all -- beyond that a fixed
 seeded choice of rows.  The inputs are seeded, so two builds given the same arguments write comparable files.
-`cpu_baseline` times the reference's own C path (oracle/_ref, built-in FFT + naive
+`cpu_baseline` (--full) times the reference's own C path (oracle/_ref, built-in FFT + naive
 double-accumulating matmul: no FFTW/MKL in this image) on the host cores for a bounded sample.
 """
 import argparse
@@ -454,11 +460,13 @@ class CpuEvent:
         return (other.t - self.t) * 1e3
 
 
-def measure(w, torch, dist, dev, world, steps, warmup, clock_warmup, sustained_s, gathers=(), which=(), dry=False, dump_dir=None):
+def measure(w, torch, dist, dev, world, steps, warmup, clock_warmup, sustained_s, gathers=(), which=(), dry=False, dump_dir=None,
+            clock_probe=True):
     """W untimed steps, then exactly `steps` steps between barrier + synchronize fences; the steps' average device time from
     ONE pair of events on the launch stream around them; optionally a back-to-back loop of >= sustained_s seconds.  With `gathers` the slabs
     of step i travel to rank 0 on a side stream while step i + 1 computes (double-buffered sources).  With `dump_dir` the results of the last
-    timed step are written there behind the closing fence, before anything else runs (dump_outputs)."""
+    timed step are written there behind the closing fence, before anything else runs (dump_outputs).  sustained_s = 0 and clock_probe =
+    False (a plain run) end the call there: nothing is launched after the timed steps."""
     Event = CpuEvent if dry else torch.cuda.Event
     sync = (lambda: None) if dry else torch.cuda.synchronize
     comm = torch.cuda.Stream(device=dev) if (gathers and not dry) else None
@@ -530,7 +538,7 @@ def measure(w, torch, dist, dev, world, steps, warmup, clock_warmup, sustained_s
     # ---- outside the timed region: the shader clock THIS device holds under THIS workload (a sleeping wave on a side stream
     # samples s_memtime against the constant reference clock while the steps below run on the other CUs: afx_clock_probe_start)
     probe = None
-    if not dry:
+    if clock_probe and not dry:
         try:
             from audioflux_amd.batch import ClockProbe
             probe = ClockProbe(torch, dev)
@@ -708,14 +716,16 @@ def dense_bank_block(torch, af, dev, check=True):
     return blk
 
 
-def device_info(torch, dev):
-    """what ran the numbers: name / arch / CU count / PCI bus id from the runtime, power cap and temperature from rocm-smi
-    when it answers within a few seconds (never a reason to lose the line)"""
+def device_info(torch, dev, smi=True):
+    """what ran the numbers: name / arch / CU count / PCI bus id from the runtime; with `smi` (--full) power cap and temperature
+    from rocm-smi when it answers within a few seconds (never a reason to lose the line)"""
     p = torch.cuda.get_device_properties(dev)
     info = {"name": p.name, "arch": getattr(p, "gcnArchName", None), "compute_units": p.multi_processor_count,
             "hbm_gib": round(p.total_memory / 2**30, 1),
             "pci_bus_id": "%04x:%02x:%02x.0" % (getattr(p, "pci_domain_id", 0), getattr(p, "pci_bus_id", 0), getattr(p, "pci_device_id", 0)),
             "hip": getattr(torch.version, "hip", None)}
+    if not smi:
+        return info
     try:
         import subprocess
         r = subprocess.run(["rocm-smi", "-d", str(dev.index or 0), "--showmaxpower", "--showpower", "--showtemp", "--json"],
@@ -750,7 +760,10 @@ def self_launch(n):
     return subprocess.call(cmd, env=env)
 
 
-def main():
+LEGS = ("sustained", "check", "cpu_baseline", "secondary", "legacy")
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -762,12 +775,16 @@ def main():
     ap.add_argument("--gather", default="", help="comma list of feature slabs gathered to rank 0 when N > 1 "
                     "(cfg 2: mfcc[,mel]; cfg 5: chroma[,cqt]); default: the first one")
     ap.add_argument("--no-gather", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sustained", action="store_true")
-    ap.add_argument("--no-check", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="--config 2 at one GPU also measures cfg 4 and cfg 5 "
-                    "after the headline (outside its timed region) and reports them under `secondary`")
-    ap.add_argument("--no-legacy", action="store_true", help="skip the reference's published benchmark through its own wrapper "
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run every leg that is not part of the headline figure: the "
+                    "sustained loop under the clock probe, the oracle check, the reference's CPU baseline, the secondary configurations and "
+                    "the dense bank (--config 2 at one GPU), the reference's published benchmark, the device's power cap and temperature; "
+                    "without it a run sets up, warms up, times the steps, writes --dump-outputs and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the reference on the host cores")
+    ap.add_argument("--no-sustained", action="store_true", help="with --full: skip the back-to-back loop and the clock probe's steps at one GPU")
+    ap.add_argument("--no-check", action="store_true", help="with --full: skip the oracle checks")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: --config 2 at one GPU also measures cfg 4, cfg 5 and the dense "
+                    "bank after the headline (outside its timed region) and reports them under `secondary` and `dense_bank`; skip them")
+    ap.add_argument("--no-legacy", action="store_true", help="with --full: skip the reference's published benchmark through its own wrapper "
                     "(tools/legacy_bench.py; --config 2 at one GPU)")
     ap.add_argument("--n1-value", type=float, default=0.0, help="the N = 1 value of the same configuration (BENCH line): with N > 1 the "
                     "line then carries efficiency_vs_n1 = value / (N x n1-value), the weak-scaling efficiency north_star asks for")
@@ -777,9 +794,17 @@ def main():
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last of them computed (rank 0's "
                     "arrays, as a caller receives them) to DIR/<name>.npy, float32, at most 64 MB in all: beyond that a fixed seeded "
                     "choice of rows")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.steps < 1:
         ap.error("--steps: the rate is units x steps / the time of exactly that many steps, so at least 1")
+    # the legs beside the headline figure: none without --full; with it, those whose --no-* switch is not given
+    a.legs = {leg: a.full and not getattr(a, "no_" + leg) for leg in LEGS}
+    return a
+
+
+def main():
+    a = parse_args()
+    legs = a.legs
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: no launcher environment, so this process becomes the launcher -- the same
@@ -821,7 +846,7 @@ def main():
     gathers = ([afd.FeatureGather(dst=0, counts=counts) for _ in which] if (world > 1 and not a.no_gather) else [])
 
     m = measure(w, torch, dist, dev, world, a.steps, a.warmup, a.clock_warmup,
-                0.0 if a.no_sustained else 1.0, gathers, which, dry, a.dump_outputs if rank == 0 else None)
+                1.0 if legs["sustained"] else 0.0, gathers, which, dry, a.dump_outputs if rank == 0 else None, clock_probe=a.full)
     elapsed = m["elapsed"]
 
     # ---- outside the timed region ----------------------------------------------------------------
@@ -832,7 +857,7 @@ def main():
         want = torch.arange(total, dtype=torch.float32) * 1000 + (a.steps - 1)
         assert got.shape[0] == total and got.shape[1] == w.T and bool((got[:, 0, 0] == want).all()), "gathered slab order"
     err = None
-    if rank == 0 and not a.no_check:
+    if rank == 0 and legs["check"]:
         err = w.check(m["last"])
         assert err is None or err <= 1e-5, f"benchmarked output differs from the oracle: {err:.3e}"
 
@@ -856,10 +881,10 @@ def main():
             "rccl_ranks": dist.get_world_size() if dist.is_initialized() else 1, "steps": a.steps,
             "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps, "higher_is_better": True,
             "scaling": "strong" if a.total_clips > 0 else "weak", "vs_baseline": None,
-            "dtype": getattr(w, "dtype", "f32"), "data": "synthetic",
+            "dtype": getattr(w, "dtype", "f32"), "data": "synthetic", "full": a.full,
             "config": {"workload": w.workload, "clips_per_gpu": clips, "units_per_step_per_gpu": w.units,
                        "outputs": w.outputs, "parallelism": par, "clock_warmup_s": a.clock_warmup,
-                       "device": None if dry else device_info(torch, dev)},
+                       "device": None if dry else device_info(torch, dev, smi=a.full)},
             "roofline": roofline(W, w, clips, m),
             "oracle_check": {"clip0_max_rel_err": err, "bar": 1e-5},
         }
@@ -881,12 +906,12 @@ def main():
             if a.n1_value > 0:  # weak scaling: N ranks x the one-GPU rate is 1.0
                 out["efficiency_vs_n1"] = value / (world * a.n1_value) if a.total_clips <= 0 else value / a.n1_value / world
                 out["n1_value"] = a.n1_value
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and legs["cpu_baseline"]:
             try:
                 out["cpu_baseline"] = w.cpu()
             except Exception as e:  # the baseline is a report, never a reason to lose the GPU number
                 out["cpu_baseline"] = {"error": repr(e)}
-        if world == 1 and a.config == 2 and not dry and not a.no_secondary:
+        if world == 1 and a.config == 2 and not dry and legs["secondary"]:
             # BASELINE configs[3] / [4] on the same line: measured in this process after the headline, each with
             # its own fences, device-event step time, sustained loop and oracle check (a few seconds in all)
             del w
@@ -896,8 +921,8 @@ def main():
                 try:
                     W2 = WORKLOADS[cfg]
                     w2 = W2(torch, af, dev, rank, W2.default_clips)
-                    m2 = measure(w2, torch, dist, dev, 1, k, wu, 0.3, 0.0 if a.no_sustained else 0.7)
-                    e2 = None if a.no_check else w2.check(m2["last"])
+                    m2 = measure(w2, torch, dist, dev, 1, k, wu, 0.3, 0.7 if legs["sustained"] else 0.0)
+                    e2 = w2.check(m2["last"]) if legs["check"] else None
                     assert e2 is None or e2 <= 1e-5, f"cfg {cfg}: benchmarked output differs from the oracle: {e2:.3e}"
                     r2 = roofline(W2, w2, W2.default_clips, m2)
                     out["secondary"][f"cfg{cfg}"] = {
@@ -906,7 +931,7 @@ def main():
                         "dtype": getattr(w2, "dtype", "f32"), "frac": r2["frac"], "sustained_frac": r2["sustained_frac"],
                         "traffic": r2["traffic"], "traffic_over_algorithmic": r2["traffic_over_algorithmic"],
                         "roofline": r2, "oracle_check": {"clip0_max_rel_err": e2, "bar": 1e-5}}
-                    if not a.no_cpu_baseline:  # the reference on the host cores, a few seconds per configuration
+                    if legs["cpu_baseline"]:  # the reference on the host cores, a few seconds per configuration
                         try:
                             out["secondary"][f"cfg{cfg}"]["cpu_baseline"] = w2.cpu(budget_s=6.0)
                         except Exception as e:
@@ -915,13 +940,13 @@ def main():
                     torch.cuda.empty_cache()
                 except Exception as e:  # never lose the headline line to a secondary configuration
                     out["secondary"][f"cfg{cfg}"] = {"error": repr(e)}
-        if world == 1 and a.config == 2 and not dry and not a.no_secondary:
+        if world == 1 and a.config == 2 and not dry and legs["secondary"]:
             try:  # the dense filter-bank route and its MFMA product (a few seconds; never a reason to lose the line)
-                out["dense_bank"] = dense_bank_block(torch, af, dev, check=not a.no_check)
+                out["dense_bank"] = dense_bank_block(torch, af, dev, check=legs["check"])
             except Exception as e:
                 out["dense_bank"] = {"error": repr(e)}
             torch.cuda.empty_cache()
-        if world == 1 and a.config == 2 and not dry and not a.no_legacy:
+        if world == 1 and a.config == 2 and not dry and legs["legacy"]:
             # the reference's own published benchmark through its unmodified wrapper + this library (host pointers, one
             # clip per call, PCIe inside the clock) -- a fresh interpreter, after everything else
             import subprocess

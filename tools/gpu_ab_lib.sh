@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/call_$TAG; mkdir -p $OUT
 V=$PWD/audioflux_amd/lib/variants
 one() { local label=$1; shift
-  env "$@" timeout -k 10 200 python bench.py --no-cpu-baseline --no-secondary --no-legacy --steps 20 --warmup 5 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('$label: value %.5g ms/step %.4f kernel_ms %.4f sustained_ms %.4f check %s'%(d['value'],d['ms_per_step'],r['kernel_ms'],r['sustained_ms'],d['oracle_check']['clip0_max_rel_err']))"
+  env "$@" timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-secondary --no-legacy --steps 20 --warmup 5 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('$label: value %.5g ms/step %.4f kernel_ms %.4f sustained_ms %.4f check %s'%(d['value'],d['ms_per_step'],r['kernel_ms'],r['sustained_ms'],d['oracle_check']['clip0_max_rel_err']))"
 }
 for i in $(seq $R); do
   one shipped AFX_X=0 | tee -a $OUT/ab.txt
