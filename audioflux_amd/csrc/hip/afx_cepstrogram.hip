@@ -94,9 +94,9 @@ __global__ void k_cepstrogram(AfxCepstrogramArgs a) {
     }
 }
 
-// ---- N = 2048 and N = 4096: one wave per frame, wave-level real transforms -----------------
-// Every sequence of the chain is real, so each transform is built from the 1024-point complex
-// transform of afx_wavefft2048.h (registers + two LDS exchanges, no workgroup barrier) instead of
+// ---- N = 512 .. 4096: one wave per frame, wave-level real transforms ------------------------
+// Every sequence of the chain is real, so each transform is built from the complex wave transform of
+// afx_wavefft2048.h / afx_wavefft_small.h (registers + LDS exchanges, no workgroup barrier) instead of
 // an N-point complex radix-2 transform in LDS with a barrier per stage pair:
 //   S = rfft(x w)                    -> L[k] = ln max(|S[k]|^2, 1e-16), k <= N/2
 //   L is real and even (L[N - k] = L[k]), so IFFT(L) = FFT(L) / N is real and even:
@@ -110,15 +110,19 @@ __global__ void k_cepstrogram(AfxCepstrogramArgs a) {
 //   out3[k] = L[k] - out2[k] + c[q] cos(2 pi k q / N)      (index N-q is in both sequences;
 //                                                            q = 0: out3 = L - c[0])
 // with cos(m theta_k) by rotating W_N^k (an error of ~m ulp; q <= 16) -- two transforms per frame.
+// Only n_fft 2048 has the lifter transforms as well; elsewhere a larger cepNum takes the size-generic kernel.
 // Between the transforms the spectrum / cepstrum goes through an (N/2 + 1)-float natural-order
 // row in the wave's exchange buffer.  HBM per frame: 4 hop in (frames overlap in L2), 12 (N/2 + 1) out.
 // N = 4096 splits every transform into the 2048-point real transforms E, O of the even / odd
-// samples: X[k] = E[k] + W_4096^k O[k], X[2048 - k] = conj(E[k] - W_4096^k O[k]); it has the
-// closed-form lifters only (larger cepNum takes the size-generic kernel).
+// samples: X[k] = E[k] + W_4096^k O[k], X[2048 - k] = conj(E[k] - W_4096^k O[k]).
+// N = 1024 and 512 (round 6): the size-generic kernel ran these at 0.08-0.09 of the HBM roofline.
+// Which bin a register of a transform holds is the business of the slot views beside the transforms (afxw::Bins,
+// afxw::Bins4096, afxws::Bins<NJ>); the steps below are written once over a view.
 // (waves per workgroup 4 / 8 / 12, lifter batches of 10 / 20 bins and the fast logarithm were measured as
 // compile-time variants in round 1: profiles/r01_cepstrogram_wave.txt)
 constexpr int CW = 8;     // waves per workgroup, N = 2048 (the tables are shared)
 constexpr int CW4 = 8;    // N = 4096
+constexpr int CWS = 8;    // N = 1024, 512
 constexpr int LNB = 20;   // bins per batch of the closed-form lifters (divides 20)
 constexpr int DIRECT_Q = 16;       // largest cepNum of the closed-form lifters
 
@@ -127,7 +131,7 @@ struct CepWArgs {
     long long clipStride, totalFrames;
     int framesPerClip, hop, framesPerWave, aligned, cepNum;
     const float *win;    // [N]
-    const float2 *tab;   // afxw tables: tw1 | tw2 | tw3 ( | W_4096^k, k <= 1024, for N = 4096)
+    const float2 *tab;   // the transform's tables (afxw: tw1 | tw2 | tw3 ( | W_4096^k, k <= 1024, for N = 4096))
     float *out1, *out2, *out3;
 };
 
@@ -165,252 +169,134 @@ __device__ __forceinline__ void lifters_direct(const float *c, int q, const v2 (
     }
 }
 
-__global__ __launch_bounds__(CW * 64) void k_cepstrogram_w2048(CepWArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    constexpr int N = 2048, F = 1025;
-    v2 *tabWin = reinterpret_cast<v2 *>(smem_raw);
-    v2 *tabTw = tabWin + 1024;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform: frame counters and row pointers stay scalar)
-    v2 *ex = tabTw + afxw::TAB_F2 + wave * afxw::EX_F2;
-    float *row = reinterpret_cast<float *>(ex);  // natural-order row between transforms (1025 floats)
-    {
-        const float2 *win2 = reinterpret_cast<const float2 *>(a.win);
-        for (int i = threadIdx.x; i < 1024; i += CW * 64) tabWin[i] = v2{win2[i].x, win2[i].y};
-        for (int i = threadIdx.x; i < afxw::TAB_F2; i += CW * 64) tabTw[i] = v2{a.tab[i].x, a.tab[i].y};
-    }
-    __syncthreads();
-    const afxw::Tables tb = {tabTw, tabTw + afxw::TAB_TW1_F2, tabTw + afxw::TAB_TW1_F2 + afxw::TAB_TW2_F2};
+// LDS of a workgroup of W waves: the window (N floats) | TAB_F2 float2 of twiddle tables (TAB_LOAD of them loaded) | W exchange
+// images of EX_F2 float2, the head of each doubling as the wave's natural-order row between transforms (N/2 + 1 floats)
+template <int N, int W, int TAB_F2, int EX_F2, int TAB_LOAD = TAB_F2>
+struct CepWave {
+    v2 *tabWin, *tabTw, *ex;
+    float *row;
+    int lane;
+    long long f, fEnd;  // this wave's frames
 
-    const long long gw = (long long)blockIdx.x * CW + wave;
-    long long f = gw * a.framesPerWave, fEnd = f + a.framesPerWave;
-    if (fEnd > a.totalFrames) fEnd = a.totalFrames;
-    if (f >= fEnd) return;
-    auto frame_ptr = [&](long long fr) {
-        return a.framesPerClip > 0
-                   ? a.x + (fr / a.framesPerClip) * a.clipStride + (fr % a.framesPerClip) * (long long)a.hop
-                   : a.x + fr * (long long)a.hop;
-    };
-    v2 raw[16];
-    auto fetch = [&](const float *px) {
-        if (a.aligned) {
-            const v2 *p2 = reinterpret_cast<const v2 *>(px);
+    // tables into the LDS (all waves); false: no frame left for this wave
+    __device__ __forceinline__ bool begin(unsigned char *smem, const CepWArgs &a) {
+        tabWin = reinterpret_cast<v2 *>(smem);
+        tabTw = tabWin + N / 2;
+        lane = threadIdx.x & 63;
+        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform: frame counters and row pointers stay scalar)
+        ex = tabTw + TAB_F2 + wave * EX_F2;
+        row = reinterpret_cast<float *>(ex);
+        const float2 *win2 = reinterpret_cast<const float2 *>(a.win);
+        for (int i = threadIdx.x; i < N / 2; i += W * 64) tabWin[i] = v2{win2[i].x, win2[i].y};
+        for (int i = threadIdx.x; i < TAB_LOAD; i += W * 64) tabTw[i] = v2{a.tab[i].x, a.tab[i].y};
+        __syncthreads();
+        const long long gw = (long long)blockIdx.x * W + wave;
+        f = gw * a.framesPerWave, fEnd = f + a.framesPerWave;
+        if (fEnd > a.totalFrames) fEnd = a.totalFrames;
+        return f < fEnd;
+    }
+};
+
+__device__ __forceinline__ const float *frame_ptr(const CepWArgs &a, long long fr) {
+    return a.framesPerClip > 0 ? a.x + (fr / a.framesPerClip) * a.clipStride + (fr % a.framesPerClip) * (long long)a.hop
+                               : a.x + fr * (long long)a.hop;
+}
+
+// a frame into registers, V (float2 / float4) per lane and load: raw[r] = samples VW (64 r + lane) ..; vector loads where every
+// frame start is aligned to them
+template <typename V, int NR>
+__device__ __forceinline__ void fetch(V (&raw)[NR], const float *px, int aligned, int lane) {
+    constexpr int VW = sizeof(V) / sizeof(float);
+    if (aligned) {
+        const V *p = reinterpret_cast<const V *>(px);
 #pragma unroll
-            for (int n1 = 0; n1 < 16; ++n1) raw[n1] = p2[64 * n1 + lane];
-        } else {
+        for (int r = 0; r < NR; ++r) raw[r] = p[64 * r + lane];
+    } else {
 #pragma unroll
-            for (int n1 = 0; n1 < 16; ++n1) raw[n1] = v2{px[2 * (64 * n1 + lane)], px[2 * (64 * n1 + lane) + 1]};
+        for (int r = 0; r < NR; ++r)
+#pragma unroll
+            for (int c = 0; c < VW; ++c) raw[r][c] = px[VW * (64 * r + lane) + c];
+    }
+}
+
+// One value per bin slot of layout V -> a natural-order row (in the LDS, or of an output).  Every copy a lane holds is stored, in
+// slot order: of the bins lane 0 holds twice (afxw::Bins: equal up to rounding) the later store wins, as it always has.
+template <class V>
+__device__ __forceinline__ void scatter(float *dst, int lane, const float (&val)[V::SLOTS]) {
+#pragma unroll
+    for (int slot = 0; slot < V::SLOTS; ++slot)
+        if (V::held(slot, lane)) dst[V::bin(slot, lane)] = val[slot];
+}
+
+// 3'. closed-form lifter outputs of every bin of layout V, at most LNB slots at a time (register pressure); twiddle(slot) = W_N^bin.
+// DROP: one slot lane 0 does not store -- see cepstrogram_wave.
+template <class V, int DROP = -1, typename Tw>
+__device__ __forceinline__ void lifter_outputs(const float *row, int q, int lane, const float (&Lk)[V::SLOTS], float *o2, float *o3, Tw twiddle) {
+    constexpr int NB = V::SLOTS < LNB ? V::SLOTS : LNB;
+    static_assert(V::SLOTS % NB == 0, "whole batches");
+#pragma unroll
+    for (int b0 = 0; b0 < V::SLOTS; b0 += NB) {
+        v2 w[NB];
+        float lk[NB], env[NB], det[NB];
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            w[i] = twiddle(b0 + i);
+            lk[i] = Lk[b0 + i];
         }
-    };
-    // one value per bin of a transform, in the lane layout of afxw::Bins: slot 8 s + j is bin
-    // k = lane + 64 s + 256 j, slot 16 + 8 s + j... see bin_of()
-    // -> natural-order row
-    auto to_row = [&](const afxw::Bins &b, auto val) {
+        lifters_direct<NB>(row, q, w, lk, env, det);
 #pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int k = lane + 64 * s + 256 * j;
-                row[k] = val(b.x[s][j]);
-                row[1024 - k] = val(b.y[s][j]);
+        for (int i = 0; i < NB; ++i) {
+            const int slot = b0 + i;
+            if (V::held(slot, lane) && !(slot == DROP && lane == 0)) {
+                if (o2) o2[V::bin(slot, lane)] = env[i];
+                if (o3) o3[V::bin(slot, lane)] = det[i];
             }
-        if (lane == 0) {
-            row[128] = val(b.xc[0]);
-            row[896] = val(b.yc[0]);
-            row[384] = val(b.xc[1]);
-            row[640] = val(b.yc[1]);
-        }
-    };
-    // real parts of one transform -> out[0..1024] of this frame
-    auto to_out = [&](const afxw::Bins &b, float *out, float scale) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int k = lane + 64 * s + 256 * j;
-                out[k] = b.x[s][j].x * scale;
-                out[1024 - k] = b.y[s][j].x * scale;
-            }
-        if (lane == 0) {
-            out[128] = b.xc[0].x * scale;
-            out[896] = b.yc[0].x * scale;
-            out[384] = b.xc[1].x * scale;
-            out[640] = b.yc[1].x * scale;
-        }
-    };
-    const int q = a.cepNum;
-    const bool direct = q <= DIRECT_Q;
-    fetch(frame_ptr(f));
-    for (; f < fEnd; ++f) {
-        v2 v[16];
-#pragma unroll
-        for (int n1 = 0; n1 < 16; ++n1) v[n1] = raw[n1] * tabWin[64 * n1 + lane];
-        if (f + 1 < fEnd) fetch(frame_ptr(f + 1));  // in flight under the transforms
-        afxw::Bins b;
-        // 1. spectrum -> log power row
-        afxw::rfft2048(v, ex, tb, lane, b);
-        float Lk[20];  // slots: 8 s + j -> bin k, 8 s + 4 + j -> bin 1024 - k, 16..19 -> 128, 896, 384, 640
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                Lk[8 * s + j] = log_power(b.x[s][j]);
-                Lk[8 * s + 4 + j] = log_power(b.y[s][j]);
-            }
-        Lk[16] = log_power(b.xc[0]);
-        Lk[17] = log_power(b.yc[0]);
-        Lk[18] = log_power(b.xc[1]);
-        Lk[19] = log_power(b.yc[1]);
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int k = lane + 64 * s + 256 * j;
-                row[k] = Lk[8 * s + j];
-                row[1024 - k] = Lk[8 * s + 4 + j];
-            }
-        if (lane == 0) {
-            row[128] = Lk[16];
-            row[896] = Lk[17];
-            row[384] = Lk[18];
-            row[640] = Lk[19];
-        }
-        wave_lds_order();
-        // 2. real cepstrum: rfft of the even extension L[m] = L[2048 - m]
-#pragma unroll
-        for (int n1 = 0; n1 < 16; ++n1) {
-            const int m = 2 * (64 * n1 + lane);
-            v[n1] = v2{row[m <= 1024 ? m : N - m], row[m + 1 <= 1024 ? m + 1 : N - m - 1]};
-        }
-        wave_lds_order();
-        afxw::rfft2048(v, ex, tb, lane, b);
-        const float invN = 1.f / (float)N;
-        if (a.out1) to_out(b, a.out1 + f * F, invN);
-        if (!a.out2 && !a.out3) continue;
-        to_row(b, [invN](v2 z) { return z.x * invN; });
-        wave_lds_order();
-        if (direct) {
-            // 3'. closed-form lifters; W_2048^k = 2 tab3[k], W_2048^(1024 - k) = -conj(W_2048^k);
-            //     slots as in Lk[], LNB at a time (register pressure)
-            float *o2 = a.out2 ? a.out2 + f * F : nullptr, *o3 = a.out3 ? a.out3 + f * F : nullptr;
-#pragma unroll
-            for (int b0 = 0; b0 < 20; b0 += LNB) {
-                v2 w[LNB];
-                float lk[LNB], env[LNB], det[LNB];
-#pragma unroll
-                for (int i = 0; i < LNB; ++i) {
-                    const int slot = b0 + i;
-                    const int kb = slot < 16 ? lane + 64 * (slot >> 3) + 256 * (slot & 3) : 128 + 256 * ((slot - 16) >> 1);
-                    const bool partner = slot < 16 ? ((slot >> 2) & 1) : ((slot - 16) & 1);
-                    const v2 t = tb.tw3[kb] * 2.f;
-                    w[i] = partner ? v2{-t.x, t.y} : t;
-                    lk[i] = Lk[slot];
-                }
-                lifters_direct<LNB>(row, q, w, lk, env, det);
-#pragma unroll
-                for (int i = 0; i < LNB; ++i) {
-                    const int slot = b0 + i;
-                    const int kb = slot < 16 ? lane + 64 * (slot >> 3) + 256 * (slot & 3) : 128 + 256 * ((slot - 16) >> 1);
-                    const bool partner = slot < 16 ? ((slot >> 2) & 1) : ((slot - 16) & 1);
-                    const int k = partner ? 1024 - kb : kb;
-                    if (slot < 16 || lane == 0) {
-                        if (o2) o2[k] = env[i];
-                        if (o3) o3[k] = det[i];
-                    }
-                }
-            }
-            wave_lds_order();  // the row is read; the next frame's transform may overwrite it
-            continue;
-        }
-        // 3. lifters: l keeps c[0..q] and its mirror l[N-1-j] = c[j+1], j < q (:258-263);
-        //    d keeps c[q+1 .. N-q] (:282-283)
-        v2 vd[16];
-#pragma unroll
-        for (int n1 = 0; n1 < 16; ++n1) {
-            const int m = 2 * (64 * n1 + lane);
-            const float c0 = row[m <= 1024 ? m : N - m], c1 = row[m + 1 <= 1024 ? m + 1 : N - m - 1];
-            const bool l0 = m <= q || m >= N - q, l1 = m + 1 <= q || m + 1 >= N - q;
-            const bool d0 = m >= q + 1 && m <= N - q, d1 = m + 1 >= q + 1 && m + 1 <= N - q;
-            v[n1] = v2{l0 ? c0 : 0.f, l1 ? c1 : 0.f};
-            vd[n1] = v2{d0 ? c0 : 0.f, d1 ? c1 : 0.f};
-        }
-        wave_lds_order();
-        if (a.out2) {
-            afxw::rfft2048(v, ex, tb, lane, b);
-            to_out(b, a.out2 + f * F, 1.f);
-        }
-        if (a.out3) {
-            afxw::rfft2048(vd, ex, tb, lane, b);
-            to_out(b, a.out3 + f * F, 1.f);
         }
     }
 }
 
-// ---- N = 1024 and N = 512: the same chain on the wave transforms of the fused STFT kernels at those sizes (afx_wavefft_small.h;
-// round 6 -- the size-generic kernel ran these at 0.08-0.09 of the HBM roofline).  Closed-form lifters only (cepNum <= DIRECT_Q;
-// larger cepNum takes the size-generic kernel).  Bin layout: k = lane + 64 j and its partner N/2 - k, j < NJ, + bin N/4 in every lane.
-constexpr int CWS = 8;  // waves per workgroup
-
-template <class X>
-__global__ __launch_bounds__(CWS * 64) void k_cepstrogram_wsmall(CepWArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    constexpr int N = X::N, M = X::M, F = M + 1, NR = X::NR, NJ = X::NJ, NB = 2 * NJ + 1;
-    v2 *tabWin = reinterpret_cast<v2 *>(smem_raw);
-    v2 *tabTw = tabWin + M;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    v2 *ex = tabTw + X::TAB_F2 + wave * X::EX_F2;
-    float *row = reinterpret_cast<float *>(ex);  // natural-order row between transforms (F floats)
-    {
-        const float2 *win2 = reinterpret_cast<const float2 *>(a.win);
-        for (int i = threadIdx.x; i < M; i += CWS * 64) tabWin[i] = v2{win2[i].x, win2[i].y};
-        for (int i = threadIdx.x; i < X::TAB_F2; i += CWS * 64) tabTw[i] = v2{a.tab[i].x, a.tab[i].y};
+// the 2048-point transform in the shape of afxws::Fft1k / Fft512
+struct Fft2k {
+    static constexpr int N = 2048, M = 1024, NR = 16, TAB_F2 = afxw::TAB_F2, EX_F2 = afxw::EX_F2;
+    typedef afxw::Bins B;
+    static __device__ __forceinline__ const v2 *tw3_of(const v2 *tab) { return tab + afxw::TAB_TW1_F2 + afxw::TAB_TW2_F2; }
+    static __device__ __forceinline__ void rfft(v2 (&v)[16], v2 *ex, const v2 *tab, int lane, B &o) {
+        const afxw::Tables tb = {tab, tab + afxw::TAB_TW1_F2, tw3_of(tab)};
+        afxw::rfft2048(v, ex, tb, lane, o);
     }
-    __syncthreads();
-    const v2 *tw3 = X::tw3_of(tabTw);  // 0.5 W_N^k, k <= N/4
+};
 
-    const long long gw = (long long)blockIdx.x * CWS + wave;
-    long long f = gw * a.framesPerWave, fEnd = f + a.framesPerWave;
-    if (fEnd > a.totalFrames) fEnd = a.totalFrames;
-    if (f >= fEnd) return;
-    auto frame_ptr = [&](long long fr) {
-        return a.framesPerClip > 0
-                   ? a.x + (fr / a.framesPerClip) * a.clipStride + (fr % a.framesPerClip) * (long long)a.hop
-                   : a.x + fr * (long long)a.hop;
-    };
-    v2 raw[NR];
-    auto fetch = [&](const float *px) {
-        if (a.aligned) {
-            const v2 *p2 = reinterpret_cast<const v2 *>(px);
-#pragma unroll
-            for (int r = 0; r < NR; ++r) raw[r] = p2[64 * r + lane];
-        } else {
-#pragma unroll
-            for (int r = 0; r < NR; ++r) raw[r] = v2{px[2 * (64 * r + lane)], px[2 * (64 * r + lane) + 1]};
-        }
-    };
+// ---- N = 2048, 1024, 512: one transform per step.  X: Fft2k, afxws::Fft1k, afxws::Fft512.
+// DROP: at 2048 the closed-form lifter outputs were stored all x[s][..], then all y[s][..], which left bin 768 of lane 0 to
+// y[0][1]; pair by pair x[0][3] (slot 6) would come later, so lane 0 leaves it out there.  (Rows and transform outputs were stored
+// pair by pair from the start and take every copy.)  The two copies agree to rounding; the choice only keeps the output bits.
+template <class X, int W, int DROP>
+__device__ __forceinline__ void cepstrogram_wave(unsigned char *smem, const CepWArgs &a) {
+    typedef typename X::B V;
+    constexpr int N = X::N, M = X::M, F = M + 1, NR = X::NR, NB = V::SLOTS;
+    CepWave<N, W, X::TAB_F2, X::EX_F2> cw;
+    if (!cw.begin(smem, a)) return;
+    const int lane = cw.lane;
+    v2 *ex = cw.ex;
+    const v2 *tabWin = cw.tabWin, *tabTw = cw.tabTw;
+    float *row = cw.row;
+    const v2 *tw3 = X::tw3_of(tabTw);  // 0.5 W_N^k, k <= N/4 at least
     const int q = a.cepNum;
     const float invN = 1.f / (float)N;
-    fetch(frame_ptr(f));
-    for (; f < fEnd; ++f) {
+    const long long fEnd = cw.fEnd;
+    v2 raw[NR];
+    fetch(raw, frame_ptr(a, cw.f), a.aligned, lane);
+    for (long long f = cw.f; f < fEnd; ++f) {
         v2 v[NR];
 #pragma unroll
         for (int r = 0; r < NR; ++r) v[r] = raw[r] * tabWin[64 * r + lane];
-        if (f + 1 < fEnd) fetch(frame_ptr(f + 1));  // in flight under the transforms
-        typename X::B b;
-        // 1. spectrum -> log power row.  Slots: j -> bin k = lane + 64 j, NJ + j -> bin M - k, 2 NJ -> bin N/4
+        if (f + 1 < fEnd) fetch(raw, frame_ptr(a, f + 1), a.aligned, lane);  // in flight under the transforms
+        V b;
+        // 1. spectrum -> log power (kept in registers for the closed-form details) -> row
         X::rfft(v, ex, tabTw, lane, b);
         float Lk[NB];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            Lk[j] = log_power(b.x[j]);
-            Lk[NJ + j] = log_power(b.y[j]);
-        }
-        Lk[2 * NJ] = log_power(b.xm);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            row[lane + 64 * j] = Lk[j];
-            row[M - lane - 64 * j] = Lk[NJ + j];
-        }
-        if (lane == 0) row[N / 4] = Lk[2 * NJ];
+        b.for_each([&](int slot, v2 S) { Lk[slot] = log_power(S); });
+        scatter<V>(row, lane, Lk);
         wave_lds_order();
         // 2. real cepstrum: rfft of the even extension L[m] = L[N - m]
 #pragma unroll
@@ -420,114 +306,96 @@ __global__ __launch_bounds__(CWS * 64) void k_cepstrogram_wsmall(CepWArgs a) {
         }
         wave_lds_order();
         X::rfft(v, ex, tabTw, lane, b);
-        if (a.out1) {
-            float *o1 = a.out1 + f * F;
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                o1[lane + 64 * j] = b.x[j].x * invN;
-                o1[M - lane - 64 * j] = b.y[j].x * invN;
-            }
-            if (lane == 0) o1[N / 4] = b.xm.x * invN;
-        }
+        float ck[NB];
+        b.for_each([&](int slot, v2 C) { ck[slot] = C.x * invN; });
+        if (a.out1) scatter<V>(a.out1 + f * F, lane, ck);
         if (!a.out2 && !a.out3) continue;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            row[lane + 64 * j] = b.x[j].x * invN;
-            row[M - lane - 64 * j] = b.y[j].x * invN;
-        }
-        if (lane == 0) row[N / 4] = b.xm.x * invN;
+        scatter<V>(row, lane, ck);
         wave_lds_order();
-        // 3'. closed-form lifters; W_N^k = 2 tw3[k], W_N^(M - k) = -conj(W_N^k)
-        {
-            v2 w[NB];
-            float env[NB], det[NB];
+        if (N != 2048 || q <= DIRECT_Q) {
+            // 3'. W_N^k = 2 tw3[k], W_N^(M - k) = -conj(W_N^k)
+            lifter_outputs<V, DROP>(row, q, lane, Lk, a.out2 ? a.out2 + f * F : nullptr, a.out3 ? a.out3 + f * F : nullptr, [&](int slot) {
+                const v2 t = tw3[V::position(slot, lane)] * 2.f;
+                return V::mirrored(slot) ? v2{-t.x, t.y} : t;
+            });
+            wave_lds_order();  // the row is read; the next frame's transform may overwrite it
+            continue;
+        }
+        if constexpr (N == 2048) {
+            // 3. lifters: l keeps c[0..q] and its mirror l[N-1-j] = c[j+1], j < q (:258-263);
+            //    d keeps c[q+1 .. N-q] (:282-283)
+            v2 vd[NR];
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const v2 t = tw3[lane + 64 * j] * 2.f;
-                w[j] = t;
-                w[NJ + j] = v2{-t.x, t.y};
+            for (int r = 0; r < NR; ++r) {
+                const int m = 2 * (64 * r + lane);
+                const float c0 = row[m <= M ? m : N - m], c1 = row[m + 1 <= M ? m + 1 : N - m - 1];
+                const bool l0 = m <= q || m >= N - q, l1 = m + 1 <= q || m + 1 >= N - q;
+                const bool d0 = m >= q + 1 && m <= N - q, d1 = m + 1 >= q + 1 && m + 1 <= N - q;
+                v[r] = v2{l0 ? c0 : 0.f, l1 ? c1 : 0.f};
+                vd[r] = v2{d0 ? c0 : 0.f, d1 ? c1 : 0.f};
             }
-            w[2 * NJ] = tw3[N / 4] * 2.f;
-            lifters_direct<NB>(row, q, w, Lk, env, det);
-            float *o2 = a.out2 ? a.out2 + f * F : nullptr, *o3 = a.out3 ? a.out3 + f * F : nullptr;
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                if (o2) {
-                    o2[lane + 64 * j] = env[j];
-                    o2[M - lane - 64 * j] = env[NJ + j];
-                }
-                if (o3) {
-                    o3[lane + 64 * j] = det[j];
-                    o3[M - lane - 64 * j] = det[NJ + j];
-                }
+            wave_lds_order();
+            if (a.out2) {
+                X::rfft(v, ex, tabTw, lane, b);
+                b.for_each([&](int slot, v2 C) { ck[slot] = C.x; });
+                scatter<V>(a.out2 + f * F, lane, ck);
             }
-            if (lane == 0) {
-                if (o2) o2[N / 4] = env[2 * NJ];
-                if (o3) o3[N / 4] = det[2 * NJ];
+            if (a.out3) {
+                X::rfft(vd, ex, tabTw, lane, b);
+                b.for_each([&](int slot, v2 C) { ck[slot] = C.x; });
+                scatter<V>(a.out3 + f * F, lane, ck);
             }
         }
-        wave_lds_order();  // the row is read; the next frame's transform may overwrite it
     }
 }
 
-// ---- N = 4096 (combine4096 / bin4096: afx_wavefft2048.h) ---------------------------------------
-using afxw::bin4096;
-using afxw::combine4096;
+__global__ __launch_bounds__(CW * 64) void k_cepstrogram_w2048(CepWArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    cepstrogram_wave<Fft2k, CW, 6>(smem_raw, a);
+}
 
+template <class X>
+__global__ __launch_bounds__(CWS * 64) void k_cepstrogram_wsmall(CepWArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    cepstrogram_wave<X, CWS, -1>(smem_raw, a);
+}
+
+// ---- N = 4096: two transforms per step, combined (afxw::combine4096); closed-form lifters only
 __global__ __launch_bounds__(CW4 * 64) void k_cepstrogram_w4096(CepWArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int N = 4096, F = 2049;
     typedef float v4 __attribute__((ext_vector_type(4)));
-    v4 *tabWin = reinterpret_cast<v4 *>(smem_raw);                // [1024] window quads
-    v2 *tabTw = reinterpret_cast<v2 *>(tabWin + 1024);
-    v2 *tabW4 = tabTw + afxw::TAB_F2;                             // W_4096^k, k <= 1024 (1032 slots)
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform: frame counters and row pointers stay scalar)
-    v2 *ex = tabW4 + 1032 + wave * afxw::EX_F2;
-    float *row = reinterpret_cast<float *>(ex);  // natural-order row between transforms (2049 floats)
-    {
-        const v4 *win4 = reinterpret_cast<const v4 *>(a.win);
-        for (int i = threadIdx.x; i < 1024; i += CW4 * 64) tabWin[i] = win4[i];
-        for (int i = threadIdx.x; i < afxw::TAB_F2 + 1025; i += CW4 * 64) tabTw[i] = v2{a.tab[i].x, a.tab[i].y};
-    }
-    __syncthreads();
+    typedef afxw::Bins4096 V;
+    CepWave<N, CW4, afxw::TAB_F2 + afxw::W4_PAD_F2, afxw::EX_F2, afxw::TAB_F2 + afxw::W4_F2> cw;
+    if (!cw.begin(smem_raw, a)) return;
+    const int lane = cw.lane;
+    v2 *ex = cw.ex;
+    float *row = cw.row;
+    const v4 *tabWin = reinterpret_cast<const v4 *>(cw.tabWin);  // [1024] window quads
+    const v2 *tabTw = cw.tabTw, *tabW4 = tabTw + afxw::TAB_F2;    // W_4096^k, k <= 1024
     const afxw::Tables tb = {tabTw, tabTw + afxw::TAB_TW1_F2, tabTw + afxw::TAB_TW1_F2 + afxw::TAB_TW2_F2};
-
-    const long long gw = (long long)blockIdx.x * CW4 + wave;
-    long long f = gw * a.framesPerWave, fEnd = f + a.framesPerWave;
-    if (fEnd > a.totalFrames) fEnd = a.totalFrames;
-    if (f >= fEnd) return;
-    auto frame_ptr = [&](long long fr) {
-        return a.framesPerClip > 0
-                   ? a.x + (fr / a.framesPerClip) * a.clipStride + (fr % a.framesPerClip) * (long long)a.hop
-                   : a.x + fr * (long long)a.hop;
-    };
     const int q = a.cepNum;
-    for (; f < fEnd; ++f) {
-        const float *px = frame_ptr(f);
+    const long long fEnd = cw.fEnd;
+    for (long long f = cw.f; f < fEnd; ++f) {
         v2 ve[16], vo[16];
-        // even / odd samples of the windowed frame: lane holds x[4n .. 4n+3], n = 64 n1 + lane
+        {
+            // even / odd samples of the windowed frame: lane holds x[4n .. 4n+3], n = 64 n1 + lane
+            v4 raw[16];
+            fetch(raw, frame_ptr(a, f), a.aligned, lane);
 #pragma unroll
-        for (int n1 = 0; n1 < 16; ++n1) {
-            const int n = 64 * n1 + lane;
-            v4 xv;
-            if (a.aligned) xv = reinterpret_cast<const v4 *>(px)[n];
-            else xv = v4{px[4 * n], px[4 * n + 1], px[4 * n + 2], px[4 * n + 3]};
-            const v4 wv = tabWin[n];
-            ve[n1] = v2{xv.x * wv.x, xv.z * wv.z};
-            vo[n1] = v2{xv.y * wv.y, xv.w * wv.w};
+            for (int n1 = 0; n1 < 16; ++n1) {
+                const v4 xv = raw[n1], wv = tabWin[64 * n1 + lane];
+                ve[n1] = v2{xv.x * wv.x, xv.z * wv.z};
+                vo[n1] = v2{xv.y * wv.y, xv.w * wv.w};
+            }
         }
         afxw::Bins be, bo;
         // 1. spectrum -> log power (kept in registers for the closed-form details) -> row
         afxw::rfft2048(ve, ex, tb, lane, be);
         afxw::rfft2048(vo, ex, tb, lane, bo);
-        float Lk[40];
-        combine4096(be, bo, tabW4, lane, [&](int slot, v2 X) { Lk[slot] = log_power(X); });
-#pragma unroll
-        for (int slot = 0; slot < 32; ++slot) row[bin4096(slot, lane)] = Lk[slot];
-        if (lane == 0) {
-#pragma unroll
-            for (int slot = 32; slot < 40; ++slot) row[bin4096(slot, lane)] = Lk[slot];
-        }
+        float Lk[V::SLOTS];
+        V::for_each(be, bo, tabW4, lane, [&](int slot, v2 S) { Lk[slot] = log_power(S); });
+        scatter<V>(row, lane, Lk);
         wave_lds_order();
         // 2. real cepstrum: transform of the even extension L[m] = L[4096 - m]
 #pragma unroll
@@ -541,51 +409,20 @@ __global__ __launch_bounds__(CW4 * 64) void k_cepstrogram_w4096(CepWArgs a) {
         afxw::rfft2048(ve, ex, tb, lane, be);
         afxw::rfft2048(vo, ex, tb, lane, bo);
         const float invN = 1.f / (float)N;
-        float ck[40];
-        combine4096(be, bo, tabW4, lane, [&](int slot, v2 X) { ck[slot] = X.x * invN; });
-        float *o1 = a.out1 ? a.out1 + f * F : nullptr;
+        float ck[V::SLOTS];
+        V::for_each(be, bo, tabW4, lane, [&](int slot, v2 C) { ck[slot] = C.x * invN; });
         // only c[0 .. q] is read back (by every lane): bins 0 .. 16 live in lanes 0 .. 16, slot 0
         if (lane <= DIRECT_Q) row[lane] = ck[0];
-        if (o1) {
-#pragma unroll
-            for (int slot = 0; slot < 32; ++slot) o1[bin4096(slot, lane)] = ck[slot];
-            if (lane == 0) {
-#pragma unroll
-                for (int slot = 32; slot < 40; ++slot) o1[bin4096(slot, lane)] = ck[slot];
-            }
-        }
-        if (!a.out2 && !a.out3) {
-            wave_lds_order();
-            continue;
-        }
+        if (a.out1) scatter<V>(a.out1 + f * F, lane, ck);
         wave_lds_order();
-        // 3'. closed-form lifters, W_4096^k per slot: k', 2048 - k' -> -conj, 1024 -+ k' from the table
-        float *o2 = a.out2 ? a.out2 + f * F : nullptr, *o3 = a.out3 ? a.out3 + f * F : nullptr;
-#pragma unroll
-        for (int b0 = 0; b0 < 40; b0 += LNB) {  // LNB slots at a time: register pressure
-            v2 w[LNB];
-            float lk[LNB], env[LNB], det[LNB];
-#pragma unroll
-            for (int i = 0; i < LNB; ++i) {
-                const int slot = b0 + i;
-                const int p = slot >> 2, r = slot & 3;
-                const int kp = p < 8 ? lane + 64 * (p >> 2) + 256 * (p & 3) : 128 + 256 * (p - 8);
-                const v2 wk = tabW4[kp], wp = tabW4[1024 - kp];
-                // W^(2048 - k') = -conj(W^k'),  W^(1024 + k') = -conj(W^(1024 - k'))
-                w[i] = r == 0 ? wk : r == 1 ? v2{-wk.x, wk.y} : r == 2 ? wp : v2{-wp.x, wp.y};
-                lk[i] = Lk[slot];
-            }
-            lifters_direct<LNB>(row, q, w, lk, env, det);
-#pragma unroll
-            for (int i = 0; i < LNB; ++i) {
-                const int slot = b0 + i;
-                if (slot < 32 || lane == 0) {
-                    const int k = bin4096(slot, lane);
-                    if (o2) o2[k] = env[i];
-                    if (o3) o3[k] = det[i];
-                }
-            }
-        }
+        if (!a.out2 && !a.out3) continue;
+        // 3'. W_4096^k per slot: k', 2048 - k' -> -conj, 1024 -+ k' from the table
+        lifter_outputs<V>(row, q, lane, Lk, a.out2 ? a.out2 + f * F : nullptr, a.out3 ? a.out3 + f * F : nullptr, [&](int slot) {
+            const int kp = V::position(slot, lane), r = slot & 3;
+            const v2 wk = tabW4[kp], wp = tabW4[1024 - kp];
+            // W^(2048 - k') = -conj(W^k'),  W^(1024 + k') = -conj(W^(1024 - k'))
+            return r == 0 ? wk : r == 1 ? v2{-wk.x, wk.y} : r == 2 ? wp : v2{-wp.x, wp.y};
+        });
         wave_lds_order();  // the row is read; the next frame's transform may overwrite it
     }
 }
@@ -607,12 +444,58 @@ extern "C" void afxk_cepstrogram_fast_tables(float *tab, int fftLength) {
     if (fftLength == 4096) {
         const double PI = 3.14159265358979323846;
         float *w4 = tab + 2 * afxw::TAB_F2;
-        for (int k = 0; k <= 1024; ++k) {
+        for (int k = 0; k < afxw::W4_F2; ++k) {
             w4[2 * k] = (float)cos(-2.0 * PI * (double)k / 4096.0);
             w4[2 * k + 1] = (float)sin(-2.0 * PI * (double)k / 4096.0);
         }
     }
 }
+
+namespace {
+
+struct CepSize {  // one row per wave kernel: LDS = CepWave's layout
+    void (*kernel)(CepWArgs);
+    const char *name;
+    int N, waves, tabF2, exF2;
+    int loadMask;  // a lane's vector load is loadMask + 1 floats
+};
+const CepSize CEP_512 = {k_cepstrogram_wsmall<afxws::Fft512>, "k_cepstrogram_wsmall", 512, CWS, afxws::Fft512::TAB_F2, afxws::Fft512::EX_F2, 1};
+const CepSize CEP_1024 = {k_cepstrogram_wsmall<afxws::Fft1k>, "k_cepstrogram_wsmall", 1024, CWS, afxws::Fft1k::TAB_F2, afxws::Fft1k::EX_F2, 1};
+const CepSize CEP_2048 = {k_cepstrogram_w2048, "k_cepstrogram_w2048", 2048, CW, afxw::TAB_F2, afxw::EX_F2, 1};
+const CepSize CEP_4096 = {k_cepstrogram_w4096, "k_cepstrogram_w4096", 4096, CW4, afxw::TAB_F2 + afxw::W4_PAD_F2, afxw::EX_F2, 3};
+
+int launch_cepstrogram_wave(const CepSize &z, const AfxCepstrogramArgs *a, void *stream) {
+    CepWArgs w;
+    w.x = a->x;
+    w.clipStride = a->clipStride;
+    w.totalFrames = a->timeLength;
+    w.framesPerClip = a->framesPerClip;
+    w.hop = a->hop;
+    // vector loads (float2 / float4 per lane) need every frame start aligned to them
+    const int am = z.loadMask;
+    w.aligned = ((reinterpret_cast<size_t>(a->x) & (size_t)(4 * am + 3)) == 0 && (a->hop & am) == 0 &&
+                 (a->framesPerClip <= 0 || (a->clipStride & am) == 0))
+                    ? 1
+                    : 0;
+    w.cepNum = a->cepNum;
+    w.win = a->window;
+    w.tab = reinterpret_cast<const float2 *>(a->fastTab);
+    w.out1 = a->out1;
+    w.out2 = a->out2;
+    w.out3 = a->out3;
+    // enough waves for ~4 workgroups per CU, at most 16 frames per wave
+    long long fpw = w.totalFrames / (256LL * z.waves * 4);
+    w.framesPerWave = fpw < 1 ? 1 : (fpw > 16 ? 16 : (int)fpw);
+    const long long waves = (w.totalFrames + w.framesPerWave - 1) / w.framesPerWave;
+    const long long blocks = (waves + z.waves - 1) / z.waves;
+    const size_t lds = sizeof(float) * z.N + sizeof(float2) * (size_t)(z.tabF2 + z.waves * z.exF2);
+    AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(z.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(z.kernel, dim3((unsigned)blocks), dim3(z.waves * 64), lds, (hipStream_t)stream, w);
+    AFX_LAUNCH_CHECK(z.name);
+    return AFX_OK;
+}
+
+}  // namespace
 
 extern "C" int afxk_cepstrogram(const AfxCepstrogramArgs *a, void *stream) {
     if (a->radix2Exp < 1 || a->radix2Exp > 13) {
@@ -623,61 +506,8 @@ extern "C" int afxk_cepstrogram(const AfxCepstrogramArgs *a, void *stream) {
     const int N = 1 << a->radix2Exp;
     const bool wave2k = N == 2048 && 2 * a->cepNum + 2 < N, wave4k = N == 4096 && a->cepNum <= DIRECT_Q;
     const bool waveS = (N == 1024 || N == 512) && a->cepNum <= DIRECT_Q;
-    if ((wave2k || wave4k || waveS) && a->x && !a->specRe && a->fastTab && !afxdev_no_fused()) {
-        CepWArgs w;
-        w.x = a->x;
-        w.clipStride = a->clipStride;
-        w.totalFrames = a->timeLength;
-        w.framesPerClip = a->framesPerClip;
-        w.hop = a->hop;
-        // vector loads (float2 / float4 per lane) need every frame start aligned to them
-        const int am = (wave2k || waveS) ? 1 : 3;
-        w.aligned = ((reinterpret_cast<size_t>(a->x) & (size_t)(4 * am + 3)) == 0 && (a->hop & am) == 0 &&
-                     (a->framesPerClip <= 0 || (a->clipStride & am) == 0))
-                        ? 1
-                        : 0;
-        w.cepNum = a->cepNum;
-        w.win = a->window;
-        w.tab = reinterpret_cast<const float2 *>(a->fastTab);
-        w.out1 = a->out1;
-        w.out2 = a->out2;
-        w.out3 = a->out3;
-        const int cw = waveS ? CWS : wave2k ? CW : CW4;
-        // enough waves for ~4 workgroups per CU, at most 16 frames per wave
-        long long fpw = w.totalFrames / (256LL * cw * 4);
-        w.framesPerWave = fpw < 1 ? 1 : (fpw > 16 ? 16 : (int)fpw);
-        const long long waves = (w.totalFrames + w.framesPerWave - 1) / w.framesPerWave;
-        const long long blocks = (waves + cw - 1) / cw;
-        if (waveS) {
-            if (N == 1024) {
-                using X = afxws::Fft1k;
-                const size_t lds = sizeof(float2) * (size_t)(X::M + X::TAB_F2 + CWS * X::EX_F2);
-                AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_cepstrogram_wsmall<X>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(k_cepstrogram_wsmall<X>, dim3((unsigned)blocks), dim3(CWS * 64), lds, (hipStream_t)stream, w);
-            } else {
-                using X = afxws::Fft512;
-                const size_t lds = sizeof(float2) * (size_t)(X::M + X::TAB_F2 + CWS * X::EX_F2);
-                AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_cepstrogram_wsmall<X>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(k_cepstrogram_wsmall<X>, dim3((unsigned)blocks), dim3(CWS * 64), lds, (hipStream_t)stream, w);
-            }
-            AFX_LAUNCH_CHECK("k_cepstrogram_wsmall");
-        } else if (wave2k) {
-            const size_t lds = sizeof(float2) * (size_t)(1024 + afxw::TAB_F2 + CW * afxw::EX_F2);
-            AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_cepstrogram_w2048),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_cepstrogram_w2048, dim3((unsigned)blocks), dim3(CW * 64), lds, (hipStream_t)stream,
-                               w);
-            AFX_LAUNCH_CHECK("k_cepstrogram_w2048");
-        } else {
-            const size_t lds = 16384 + sizeof(float2) * (size_t)(afxw::TAB_F2 + 1032 + CW4 * afxw::EX_F2);
-            AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_cepstrogram_w4096),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_cepstrogram_w4096, dim3((unsigned)blocks), dim3(CW4 * 64), lds, (hipStream_t)stream,
-                               w);
-            AFX_LAUNCH_CHECK("k_cepstrogram_w4096");
-        }
-        return AFX_OK;
-    }
+    if ((wave2k || wave4k || waveS) && a->x && !a->specRe && a->fastTab && !afxdev_no_fused())
+        return launch_cepstrogram_wave(N == 512 ? CEP_512 : N == 1024 ? CEP_1024 : wave2k ? CEP_2048 : CEP_4096, a, stream);
     int threads = N / 2;
     if (threads < 64) threads = 64;
     if (threads > 512) threads = 512;

@@ -82,73 +82,211 @@ __global__ void k_istft_ola(AfxIstftArgs a) {
 // so the float32 sums round the same way -- and leaves it, divided by the window-power sum (:389-396), when frame i has been
 // added to [i hop, (i + 1) hop).  Per frame 8 N bytes in and 4 hop out (+ 4 hop of out[] read): the [frames, N] scratch round trip
 // (8 N bytes) and the second launch are gone.
+//
+// What the sizes share -- the LDS layout and its prologue, the run of frames a wave walks, the ring with its entering samples, the
+// batched add, the window-power sums and the drain -- is OlaRing below.  A kernel keeps what is its own: how the frame's bins
+// become u, which transform runs, and the walk over the transform's bin slots (the views of afx_wavefft2048.h / afx_wavefft_small.h
+// say which bin a slot is and whether this lane owns it).
 namespace {
 
 #ifndef AFX_ISTFT_WAVES
 #define AFX_ISTFT_WAVES 7
 #endif
 constexpr int IW = AFX_ISTFT_WAVES;  // waves per workgroup: 25 KB of tables (window w^e, twiddles) + <= 8 KB of window-power sums + 7 x 16.5 KB (exchange image + ring)
+constexpr int IW4 = 4;   // n_fft 4096: 16 KB window + 25 KB twiddles + <= 16 KB window-power sums + 4 x 24.5 KB (exchange image + ring)
+constexpr int ISW = 12;  // n_fft 1024 / 512 / 256 (1024: 12 x 9 KB of exchange image + ring, 11 KB of tables)
 
+// contributions to the ring that are added together.  Every output index occurs once per frame, so the slots of a batch are
+// distinct: its reads, then its writes -- written one by one the compiler must order each read behind the previous write.  The
+// batch size sets how many LDS reads are in flight and how long at / val / ok live.
+template <int CNT>
+struct OlaBatch {
+    int at[CNT];
+    float val[CNT];
+    bool ok[CNT];
+};
+
+// LDS of a workgroup of W waves: win1[N] | TAB_F2 float2 of twiddle tables (TAB_LOAD of them loaded) | W exchange images of EX_F2
+// float2 | W rings of N floats | nrmTab[hop]
+template <int N, int W, int TAB_F2, int EX_F2, int TAB_LOAD = TAB_F2>
+struct OlaRing {
+    float *win1;                       // [N] synthesis window w^e
+    const float *__restrict__ win2;    // w^(e+1), global: read at the clip's ends only
+    v2 *tabTw, *ex;                    // the transform's tables; this wave's exchange image
+    float *ring, *nrmTab, *out;
+    int lane, b, T, H, f0, f1, fs;     // clip, frames, hop; the run [f0, f1) and the first frame whose tail reaches into it
+    long long ownLo, ownHi;            // the samples this wave stores
+    int i;                             // the frame being added (at_frame)
+    long long j0;                      // its first sample
+
+    // Tables and window-power sums into the LDS (all waves), then this wave's run; false: no run left for it.  On return the ring
+    // holds the samples that enter with frame fs.
+    __device__ __forceinline__ bool begin(unsigned char *smem, const AfxIstftArgs &a, const float2 *__restrict__ tab, int framesPerRun, int runsPerClip) {
+        win1 = reinterpret_cast<float *>(smem);
+        win2 = a.win2;
+        tabTw = reinterpret_cast<v2 *>(win1 + N);
+        lane = threadIdx.x & 63;
+        const int wave = threadIdx.x >> 6;
+        ex = tabTw + TAB_F2 + wave * EX_F2;
+        ring = reinterpret_cast<float *>(tabTw + TAB_F2 + W * EX_F2) + wave * N;
+        // window-power sum of a sample every covering frame of which exists (N <= j, j / hop <= T - 1): a function of j mod hop, added
+        // in the order of k_istft_ola's loop (ascending frames = descending window positions)
+        nrmTab = ring + (W - wave) * N;  // [hop], behind the last wave's ring
+        for (int k = threadIdx.x; k < N; k += W * 64) win1[k] = a.win1[k];
+        for (int k = threadIdx.x; k < TAB_LOAD; k += W * 64) tabTw[k] = v2{tab[k].x, tab[k].y};
+        for (int t = threadIdx.x; t < a.hop; t += W * 64) {
+            float sum = 0.f;
+            for (int k = t + ((N - 1 - t) / a.hop) * a.hop; k >= 0; k -= a.hop) sum += win2[k];
+            nrmTab[t] = sum;
+        }
+        __syncthreads();
+
+        const long long run = (long long)blockIdx.x * W + wave;
+        if (run >= (long long)a.batch * runsPerClip) return false;
+        b = (int)(run / runsPerClip), T = a.timeLength, H = a.hop;
+        f0 = (int)(run - (long long)b * runsPerClip) * framesPerRun;
+        f1 = f0 + framesPerRun < T ? f0 + framesPerRun : T;
+        const int halo = (N - 1) / H;
+        fs = f0 > halo ? f0 - halo : 0;
+        const long long outLen = (long long)(T - 1) * H + N;
+        ownLo = (long long)f0 * H, ownHi = f1 == T ? outLen : (long long)f1 * H;
+        out = a.out + (long long)b * a.outStride;
+        for (int t = lane; t < N; t += 64) ring[((long long)fs * H + t) & (N - 1)] = entering((long long)fs * H + t);
+        return true;
+    }
+
+    // samples that enter the ring with a frame: the caller's values where this wave will store, zeros elsewhere
+    __device__ __forceinline__ float entering(long long j) const { return (j >= ownLo && j < ownHi) ? out[j] : 0.f; }
+
+    // the window-power sum of sample j (k_istft_ola's loop; interior samples: the table)
+    __device__ __forceinline__ float power(long long j) const {
+        if (j >= N && j / H <= T - 1) return nrmTab[(int)(j % H)];
+        long long iLo = j >= N ? (j - N) / H + 1 : 0, iHi = j / H;
+        if (iHi > T - 1) iHi = T - 1;
+        float nrm = 0.f;
+        for (long long q = iLo; q <= iHi; ++q) nrm += win2[(int)(j - q * H)];
+        return nrm;
+    }
+
+    __device__ __forceinline__ void at_frame(int frame) {
+        i = frame;
+        j0 = (long long)frame * H;
+    }
+
+    // sample n of the frame, x / (2 N) of it windowed, as entry e of a batch.  (The 0.5 of the Hermitian part rides in the scale.)
+    template <int CNT>
+    __device__ __forceinline__ void put(OlaBatch<CNT> &bt, int e, bool valid, int n, float x) const {
+        const float scale = 0.5f / (float)N;
+        bt.ok[e] = valid;
+        bt.at[e] = (int)((j0 + n) & (N - 1));
+        bt.val[e] = valid ? (x * scale) * win1[n] : 0.f;
+    }
+    template <int CNT, int USED = CNT>
+    __device__ __forceinline__ void flush(const OlaBatch<CNT> &bt) const {
+        float cur[USED];
+#pragma unroll
+        for (int e = 0; e < USED; ++e) cur[e] = bt.ok[e] ? ring[bt.at[e]] : 0.f;
+#pragma unroll
+        for (int e = 0; e < USED; ++e)
+            if (bt.ok[e]) ring[bt.at[e]] = cur[e] + bt.val[e];
+    }
+    // One bin U[bin] of the transform of u gives x[bin] = (Re U + Im U) / N and, where the bin is not its own mirror image,
+    // x[N - bin] = (Re U - Im U) / N; Z is U[bin], or its conjugate as the layouts' y registers hold it.  SPF slots fill a batch,
+    // which is then added.
+    // Two spellings of one rule.  The compiler contracts cur + val into one fma where it can prove an entry valid and leaves
+    // multiply and add where a select stays; what it proves depends on how and where the mirror's validity is written, and the last
+    // bit of the output with it.  Each size keeps the spelling it was written with: decided by the caller in the layout's terms
+    // (k' > 0: 2048, 1024, 512), or from the bin between the two entries (4096).
+    template <int SPF>
+    __device__ __forceinline__ void add_bin(OlaBatch<2 * SPF> &bt, int slot, bool owned, bool mirror, int bin, bool conjugate, v2 Z) const {
+        const int e = 2 * (slot % SPF);
+        put(bt, e, owned, bin, conjugate ? Z.x - Z.y : Z.x + Z.y);
+        put(bt, e + 1, mirror, (N - bin) & (N - 1), conjugate ? Z.x + Z.y : Z.x - Z.y);
+        if (slot % SPF == SPF - 1) flush(bt);
+    }
+    template <int SPF>
+    __device__ __forceinline__ void add_bin(OlaBatch<2 * SPF> &bt, int slot, bool owned, int bin, v2 U) const {
+        const int e = 2 * (slot % SPF);
+        put(bt, e, owned, bin, U.x + U.y);
+        put(bt, e + 1, owned && bin > 0 && bin < N / 2, (N - bin) & (N - 1), U.x - U.y);
+        if (slot % SPF == SPF - 1) flush(bt);
+    }
+
+    // samples no later frame reaches leave the ring: [i hop, (i + 1) hop), everything to the clip's end behind its last frame.
+    // SPP samples per lane at a time: their reads first, then the stores.
+    template <int SPP>
+    __device__ __forceinline__ void drain() const {
+        wave_lds_order();
+        if (i >= f0) {
+            const int cnt = i == T - 1 ? N : H;
+            for (int t0 = 0; t0 < cnt && t0 < N; t0 += 64 * SPP) {  // (t0 < N: one pass where a pass covers the frame)
+                float acc[SPP], nrm[SPP];
+#pragma unroll
+                for (int u = 0; u < SPP; ++u) {
+                    const int t = t0 + lane + 64 * u;
+                    acc[u] = t < cnt ? ring[(j0 + t) & (N - 1)] : 0.f;
+                    nrm[u] = t < cnt ? power(j0 + t) : 1.f;
+                }
+#pragma unroll
+                for (int u = 0; u < SPP; ++u) {
+                    const int t = t0 + lane + 64 * u;
+                    if (t < cnt) out[j0 + t] = acc[u] / (nrm[u] < 1e-6f ? 1.f : nrm[u]);
+                }
+            }
+        }
+        wave_lds_order();
+    }
+
+    // the next frame's new samples take the slots just stored
+    __device__ __forceinline__ void enter_next() const {
+        if (i + 1 < f1)
+            for (int t = lane; t < H; t += 64) ring[(j0 + N + t) & (N - 1)] = entering(j0 + N + t);
+    }
+    // ... requested a frame ahead (request_next before the transform, enter_next(nxt) behind the drain) where they fit eight
+    // registers per lane: hop <= 512
+    __device__ __forceinline__ void request_next(float (&nxt)[8]) const {
+        if (H <= 512 && i + 1 < f1) {
+#pragma unroll
+            for (int t = 0; t < 8; ++t) nxt[t] = lane + 64 * t < H ? entering(j0 + N + lane + 64 * t) : 0.f;
+        }
+    }
+    __device__ __forceinline__ void enter_next(const float (&nxt)[8]) const {
+        if (H > 512) return enter_next();
+        if (i + 1 < f1) {
+#pragma unroll
+            for (int t = 0; t < 8; ++t)
+                if (lane + 64 * t < H) ring[(j0 + N + lane + 64 * t) & (N - 1)] = nxt[t];
+        }
+    }
+};
+
+// ---- n_fft 2048 ----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(IW * 64) void k_istft_w2048(AfxIstftArgs a, const float2 *__restrict__ tab, int framesPerRun, int runsPerClip) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int N = 2048;
-    float *win1 = reinterpret_cast<float *>(smem_raw);  // [N] synthesis window w^e
-    const float *__restrict__ win2 = a.win2;             // w^(e+1): read at the clip's ends only
-    v2 *tabTw = reinterpret_cast<v2 *>(win1 + N);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    v2 *ex = tabTw + afxw::TAB_F2 + wave * afxw::EX_F2;
-    float *ring = reinterpret_cast<float *>(tabTw + afxw::TAB_F2 + IW * afxw::EX_F2) + wave * N;
-    // window-power sum of a sample every covering frame of which exists (N <= j, j / hop <= T - 1): a function of j mod hop, added
-    // in the order of k_istft_ola's loop (ascending frames = descending window positions)
-    float *nrmTab = ring + (IW - wave) * N;              // [hop], behind the last wave's ring
-    for (int i = threadIdx.x; i < N; i += IW * 64) win1[i] = a.win1[i];
-    for (int i = threadIdx.x; i < afxw::TAB_F2; i += IW * 64) tabTw[i] = v2{tab[i].x, tab[i].y};
-    for (int t = threadIdx.x; t < a.hop; t += IW * 64) {
-        float sum = 0.f;
-        for (int k = t + ((N - 1 - t) / a.hop) * a.hop; k >= 0; k -= a.hop) sum += win2[k];
-        nrmTab[t] = sum;
-    }
-    __syncthreads();
-    const afxw::Tables tb = {tabTw, tabTw + afxw::TAB_TW1_F2, tabTw + afxw::TAB_TW1_F2 + afxw::TAB_TW2_F2};
-
-    const long long run = (long long)blockIdx.x * IW + wave;
-    if (run >= (long long)a.batch * runsPerClip) return;
-    const int b = (int)(run / runsPerClip), T = a.timeLength, H = a.hop;
-    const int f0 = (int)(run - (long long)b * runsPerClip) * framesPerRun;
-    const int f1 = f0 + framesPerRun < T ? f0 + framesPerRun : T;
-    const int halo = (N - 1) / H;
-    const int fs = f0 > halo ? f0 - halo : 0;
-    const long long outLen = (long long)(T - 1) * H + N;
-    const long long ownLo = (long long)f0 * H, ownHi = f1 == T ? outLen : (long long)f1 * H;
-    float *out = a.out + (long long)b * a.outStride;
-    const float scale = 0.5f / (float)N;
+    OlaRing<N, IW, afxw::TAB_F2, afxw::EX_F2> ola;
+    if (!ola.begin(smem_raw, a, tab, framesPerRun, runsPerClip)) return;
+    const afxw::Tables tb = {ola.tabTw, ola.tabTw + afxw::TAB_TW1_F2, ola.tabTw + afxw::TAB_TW1_F2 + afxw::TAB_TW2_F2};
+    const int lane = ola.lane;
     const bool lane0 = lane == 0;
-
-    // samples that enter the ring with a frame: the caller's values where this wave will store, zeros elsewhere
-    auto entering = [&](long long j) { return (j >= ownLo && j < ownHi) ? out[j] : 0.f; };
-    for (int t = lane; t < N; t += 64) ring[((long long)fs * H + t) & (N - 1)] = entering((long long)fs * H + t);
     // the bins of the frame about to be transformed; the next frame's are requested behind the transform, under the overlap-add
     v2 r[16], m[16];
     auto fetch = [&](int i) {
-        const v2 *re2 = reinterpret_cast<const v2 *>(a.re + ((long long)b * T + i) * N);
-        const v2 *im2 = reinterpret_cast<const v2 *>(a.im + ((long long)b * T + i) * N);
+        const v2 *re2 = reinterpret_cast<const v2 *>(a.re + ((long long)ola.b * ola.T + i) * N);
+        const v2 *im2 = reinterpret_cast<const v2 *>(a.im + ((long long)ola.b * ola.T + i) * N);
 #pragma unroll
         for (int n1 = 0; n1 < 16; ++n1) {
             r[n1] = re2[64 * n1 + lane];
             m[n1] = im2[64 * n1 + lane];
         }
     };
-    fetch(fs);
-    const bool shortHop = H <= 512;  // the samples entering with the next frame fit eight registers per lane: requested a frame ahead
+    fetch(ola.fs);
 
-    for (int i = fs; i < f1; ++i) {
-        const long long j0 = (long long)i * H;
+    for (int i = ola.fs; i < ola.f1; ++i) {
+        ola.at_frame(i);
         float nxt[8];
-        if (shortHop && i + 1 < f1) {
-#pragma unroll
-            for (int t = 0; t < 8; ++t) nxt[t] = lane + 64 * t < H ? entering(j0 + N + lane + 64 * t) : 0.f;
-        }
-        // 2. the frame's bins -> u
+        ola.request_next(nxt);
+        // the frame's bins -> u
         v2 v[16];
 #pragma unroll
         for (int n1 = 0; n1 < 16; ++n1) {
@@ -162,90 +300,18 @@ __global__ __launch_bounds__(IW * 64) void k_istft_w2048(AfxIstftArgs a, const f
             v[n1] = v2{(r[n1].x + rx) + (m[n1].x - mx), (r[n1].y + ry) + (m[n1].y - my)};
         }
         afxw::Bins bn;
-        afxw::rfft2048(v, ex, tb, lane, bn);
-        if (i + 1 < f1) fetch(i + 1);  // (behind the transform: in flight across it the 64 registers spill)
-        // 3. x[n] = (Re U[n] + Im U[n]) / N and its mirror, windowed, into the ring.  (The 0.5 of the Hermitian part rides in scale.)
-        // (every output index occurs once per frame, so the slots of a batch of contributions are distinct: its reads, then its
-        //  writes -- written one by one the compiler must order each read behind the previous write)
-        int at[16];
-        float val[16];
-        bool ok[16];
-        auto put = [&](int e, bool valid, int n, float x) {
-            ok[e] = valid;
-            at[e] = (int)((j0 + n) & (N - 1));
-            val[e] = valid ? (x * scale) * win1[n] : 0.f;
-        };
-        auto flush = [&](int cnt) {
-            float cur[16];
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-                if (e < cnt) cur[e] = ok[e] ? ring[at[e]] : 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-                if (e < cnt && ok[e]) ring[at[e]] = cur[e] + val[e];
-        };
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int k = lane + 64 * s + 256 * j, e = 4 * j;
-                const v2 X = bn.x[s][j], Y = bn.y[s][j];  // U[k], conj(U[1024 - k])
-                // lane 0, s = 0 holds k = 0, 256, 512, 768: the partners 768, 512, 256 are its own x slots -- only 1024 is new
-                const bool partner = !(lane0 && s == 0 && j > 0);
-                put(e, true, k, X.x + X.y);
-                put(e + 1, k > 0, (N - k) & (N - 1), X.x - X.y);
-                put(e + 2, partner, 1024 - k, Y.x - Y.y);
-                put(e + 3, partner && k > 0, (1024 + k) & (N - 1), Y.x + Y.y);
-            }
-            flush(16);
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {  // bins 128 + 256 i and their partners 896 - 256 i (every lane computed them: lane 0 adds)
-            const int k = 128 + 256 * q, e = 4 * q;
-            put(e, lane0, k, bn.xc[q].x + bn.xc[q].y);
-            put(e + 1, lane0, N - k, bn.xc[q].x - bn.xc[q].y);
-            put(e + 2, lane0, 1024 - k, bn.yc[q].x - bn.yc[q].y);
-            put(e + 3, lane0, 1024 + k, bn.yc[q].x + bn.yc[q].y);
-        }
-        flush(8);
-        wave_lds_order();
-        // 4. samples no later frame reaches: [i hop, (i + 1) hop), everything to the clip's end behind its last frame
-        if (i >= f0) {
-            const int cnt = i == T - 1 ? N : H;
-            auto power = [&](long long j) {  // the window-power sum of sample j (k_istft_ola's loop; interior samples: the table)
-                if (j >= N && j / H <= T - 1) return nrmTab[(int)(j % H)];
-                long long iLo = j >= N ? (j - N) / H + 1 : 0, iHi = j / H;
-                if (iHi > T - 1) iHi = T - 1;
-                float nrm = 0.f;
-                for (long long q = iLo; q <= iHi; ++q) nrm += win2[(int)(j - q * H)];
-                return nrm;
-            };
-            for (int t0 = 0; t0 < cnt; t0 += 512) {  // eight samples per lane at a time: their reads first, then the stores
-                float acc[8], nrm[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int t = t0 + lane + 64 * u;
-                    acc[u] = t < cnt ? ring[(j0 + t) & (N - 1)] : 0.f;
-                    nrm[u] = t < cnt ? power(j0 + t) : 1.f;
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int t = t0 + lane + 64 * u;
-                    if (t < cnt) out[j0 + t] = acc[u] / (nrm[u] < 1e-6f ? 1.f : nrm[u]);
-                }
-            }
-        }
-        wave_lds_order();
-        // 1'. the next frame's new samples take the slots just stored
-        if (i + 1 < f1) {
-            if (shortHop) {
-#pragma unroll
-                for (int t = 0; t < 8; ++t)
-                    if (lane + 64 * t < H) ring[(j0 + N + lane + 64 * t) & (N - 1)] = nxt[t];
-            } else {
-                for (int t = lane; t < H; t += 64) ring[(j0 + N + t) & (N - 1)] = entering(j0 + N + t);
-            }
-        }
+        afxw::rfft2048(v, ola.ex, tb, lane, bn);
+        if (i + 1 < ola.f1) fetch(i + 1);  // (behind the transform: in flight across it the 64 registers spill)
+        // batches of 16, 16 and 8 contributions: the slots of s = 0, of s = 1, the base-128 extras
+        OlaBatch<16> bt;
+        typedef afxw::Bins V;
+        bn.for_each([&](int slot, v2 Z) {
+            const bool owned = V::owned(slot, lane);
+            ola.add_bin<8>(bt, slot, owned, owned && V::paired(slot, lane), V::bin(slot, lane), V::mirrored(slot), Z);
+        });
+        ola.flush<16, 8>(bt);
+        ola.drain<8>();
+        ola.enter_next(nxt);
     }
 }
 
@@ -253,52 +319,25 @@ __global__ __launch_bounds__(IW * 64) void k_istft_w2048(AfxIstftArgs a, const f
 // transforms of its even and odd samples (afxw::combine4096, as the forward kernels do).  A lane holds u[4n .. 4n + 3], n = 64 n1 + lane:
 // the mirrors 4096 - 4n - c are element 0 of quad 1024 - n (lane 64 - lane; lane 0: its own register 16 - n1) for c = 0 and
 // elements 3, 2, 1 of quad 1023 - n (lane 63 - lane, register 15 - n1) for c = 1, 2, 3.
-constexpr int IW4 = 4;  // waves per workgroup: 16 KB window + 25 KB twiddles + <= 16 KB window-power sums + 4 x 24.5 KB (exchange image + ring)
-
 __global__ __launch_bounds__(IW4 * 64) void k_istft_w4096(AfxIstftArgs a, const float2 *__restrict__ tab, int framesPerRun, int runsPerClip) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     typedef float v4 __attribute__((ext_vector_type(4)));
-    constexpr int N = 4096, NT = afxw::TAB_F2 + 1032;  // the wave tables + W_4096^k, k <= 1024 (padded to a 16-byte multiple)
-    float *win1 = reinterpret_cast<float *>(smem_raw);
-    const float *__restrict__ win2 = a.win2;
-    v2 *tabTw = reinterpret_cast<v2 *>(win1 + N);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    v2 *ex = tabTw + NT + wave * afxw::EX_F2;
-    float *ring = reinterpret_cast<float *>(tabTw + NT + IW4 * afxw::EX_F2) + wave * N;
-    float *nrmTab = ring + (IW4 - wave) * N;
-    for (int i = threadIdx.x; i < N; i += IW4 * 64) win1[i] = a.win1[i];
-    for (int i = threadIdx.x; i < afxw::TAB_F2 + 1025; i += IW4 * 64) tabTw[i] = v2{tab[i].x, tab[i].y};
-    for (int t = threadIdx.x; t < a.hop; t += IW4 * 64) {
-        float sum = 0.f;
-        for (int k = t + ((N - 1 - t) / a.hop) * a.hop; k >= 0; k -= a.hop) sum += win2[k];
-        nrmTab[t] = sum;
-    }
-    __syncthreads();
-    const afxw::Tables tb = {tabTw, tabTw + afxw::TAB_TW1_F2, tabTw + afxw::TAB_TW1_F2 + afxw::TAB_TW2_F2};
-    const v2 *tabW4 = tabTw + afxw::TAB_F2;
-
-    const long long run = (long long)blockIdx.x * IW4 + wave;
-    if (run >= (long long)a.batch * runsPerClip) return;
-    const int b = (int)(run / runsPerClip), T = a.timeLength, H = a.hop;
-    const int f0 = (int)(run - (long long)b * runsPerClip) * framesPerRun;
-    const int f1 = f0 + framesPerRun < T ? f0 + framesPerRun : T;
-    const int halo = (N - 1) / H;
-    const int fs = f0 > halo ? f0 - halo : 0;
-    const long long outLen = (long long)(T - 1) * H + N;
-    const long long ownLo = (long long)f0 * H, ownHi = f1 == T ? outLen : (long long)f1 * H;
-    float *out = a.out + (long long)b * a.outStride;
-    const float scale = 0.5f / (float)N;
+    typedef afxw::Bins4096 V;
+    constexpr int N = 4096;
+    OlaRing<N, IW4, afxw::TAB_F2 + afxw::W4_PAD_F2, afxw::EX_F2, afxw::TAB_F2 + afxw::W4_F2> ola;
+    if (!ola.begin(smem_raw, a, tab, framesPerRun, runsPerClip)) return;
+    const afxw::Tables tb = {ola.tabTw, ola.tabTw + afxw::TAB_TW1_F2, ola.tabTw + afxw::TAB_TW1_F2 + afxw::TAB_TW2_F2};
+    const v2 *tabW4 = ola.tabTw + afxw::TAB_F2;
+    const int lane = ola.lane;
     const bool lane0 = lane == 0;
-    auto entering = [&](long long j) { return (j >= ownLo && j < ownHi) ? out[j] : 0.f; };
-    for (int t = lane; t < N; t += 64) ring[((long long)fs * H + t) & (N - 1)] = entering((long long)fs * H + t);
 
-    for (int i = fs; i < f1; ++i) {
-        const long long j0 = (long long)i * H;
+    for (int i = ola.fs; i < ola.f1; ++i) {
+        ola.at_frame(i);
         afxw::Bins be, bo;
         {
             // the frame's bins -> u: even samples (u[4n], u[4n + 2]) and odd samples (u[4n + 1], u[4n + 3]) of every quad
-            const v4 *re4 = reinterpret_cast<const v4 *>(a.re + ((long long)b * T + i) * N);
-            const v4 *im4 = reinterpret_cast<const v4 *>(a.im + ((long long)b * T + i) * N);
+            const v4 *re4 = reinterpret_cast<const v4 *>(a.re + ((long long)ola.b * ola.T + i) * N);
+            const v4 *im4 = reinterpret_cast<const v4 *>(a.im + ((long long)ola.b * ola.T + i) * N);
             v4 r[16], m[16];
 #pragma unroll
             for (int n1 = 0; n1 < 16; ++n1) {
@@ -320,126 +359,41 @@ __global__ __launch_bounds__(IW4 * 64) void k_istft_w4096(AfxIstftArgs a, const 
                 ve[n1] = v2{(r[n1].x + r0) + (m[n1].x - m0), (r[n1].z + r2) + (m[n1].z - m2)};
                 vo[n1] = v2{(r[n1].y + r1) + (m[n1].y - m1), (r[n1].w + r3) + (m[n1].w - m3)};
             }
-            afxw::rfft2048(ve, ex, tb, lane, be);
-            afxw::rfft2048(vo, ex, tb, lane, bo);
+            afxw::rfft2048(ve, ola.ex, tb, lane, be);
+            afxw::rfft2048(vo, ola.ex, tb, lane, bo);
         }
-        // x[n] = (Re U[n] + Im U[n]) / N and its mirror N - n, windowed, into the ring: 16 contributions at a time (distinct slots:
-        // their reads, then their writes)
-        int at[16];
-        float val[16];
-        bool ok[16];
-        int fill = 0;
-        auto flush = [&]() {
-            float cur[16];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) cur[e] = ok[e] ? ring[at[e]] : 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-                if (ok[e]) ring[at[e]] = cur[e] + val[e];
-        };
-        afxw::combine4096(be, bo, tabW4, lane, [&](int slot, v2 X) {
-            const int p = slot >> 2, rr = slot & 3;
-            const int kp = p < 8 ? lane + 64 * (p >> 2) + 256 * (p & 3) : 128 + 256 * (p - 8);
-            const int bin = afxw::bin4096(slot, lane);
-            // lane 0 at p < 4 holds kp = 0, 256, 512, 768: their partners 1024 -+ kp are its own slots of 4 - j (kp = 0: 1024 once);
-            // the positions 128 + 256 i are lane 0's alone
-            bool valid = p < 8 || lane0;
-            if (lane0 && p < 4 && p > 0 && rr >= 2) valid = false;
-            if (p < 8 && kp == 0 && rr == 3) valid = false;
-            const int e = 2 * (slot & 7);
-            ok[e] = valid;
-            at[e] = (int)((j0 + bin) & (N - 1));
-            val[e] = valid ? ((X.x + X.y) * scale) * win1[bin & (N - 1)] : 0.f;
-            const bool mirror = valid && bin > 0 && bin < 2048;
-            ok[e + 1] = mirror;
-            at[e + 1] = (int)((j0 + N - bin) & (N - 1));
-            val[e + 1] = mirror ? ((X.x - X.y) * scale) * win1[(N - bin) & (N - 1)] : 0.f;
-            if ((slot & 7) == 7) flush();
-            (void)fill;
-        });
-        wave_lds_order();
-        if (i >= f0) {
-            const int cnt = i == T - 1 ? N : H;
-            auto power = [&](long long j) {
-                if (j >= N && j / H <= T - 1) return nrmTab[(int)(j % H)];
-                long long iLo = j >= N ? (j - N) / H + 1 : 0, iHi = j / H;
-                if (iHi > T - 1) iHi = T - 1;
-                float nrm = 0.f;
-                for (long long q = iLo; q <= iHi; ++q) nrm += win2[(int)(j - q * H)];
-                return nrm;
-            };
-            for (int t0 = 0; t0 < cnt; t0 += 512) {
-                float acc[8], nrm[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int t = t0 + lane + 64 * u;
-                    acc[u] = t < cnt ? ring[(j0 + t) & (N - 1)] : 0.f;
-                    nrm[u] = t < cnt ? power(j0 + t) : 1.f;
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int t = t0 + lane + 64 * u;
-                    if (t < cnt) out[j0 + t] = acc[u] / (nrm[u] < 1e-6f ? 1.f : nrm[u]);
-                }
-            }
-        }
-        wave_lds_order();
-        if (i + 1 < f1)
-            for (int t = lane; t < H; t += 64) ring[(j0 + N + t) & (N - 1)] = entering(j0 + N + t);
+        // 16 contributions every 8 slots, from inside the combination
+        OlaBatch<16> bt;
+        V::for_each(be, bo, tabW4, lane, [&](int slot, v2 U) { ola.add_bin<8>(bt, slot, V::owned(slot, lane), V::bin(slot, lane), U); });
+        ola.drain<8>();
+        ola.enter_next();
     }
 }
 
 // ---- n_fft 1024 / 512: the same scheme on the wave transforms of afx_wavefft_small.h (8 x 8 x 8 in eight registers, 4 x 4 x 4 x 4
 // in four).  Their bins come out once each: k = lane + 64 j < N / 4 with its partner N / 2 - k, N / 4 in every lane.
-constexpr int ISW = 12;  // waves per workgroup (1024: 12 x 9 KB of exchange image + ring, 11 KB of tables)
-
 template <class F>
 __global__ __launch_bounds__(ISW * 64) void k_istft_wsmall(AfxIstftArgs a, const float2 *__restrict__ tab, int framesPerRun, int runsPerClip) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    constexpr int N = F::N, NR = F::NR, NJ = F::NJ;
-    float *win1 = reinterpret_cast<float *>(smem_raw);
-    const float *__restrict__ win2 = a.win2;
-    v2 *tabTw = reinterpret_cast<v2 *>(win1 + N);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    v2 *ex = tabTw + F::TAB_F2 + wave * F::EX_F2;
-    float *ring = reinterpret_cast<float *>(tabTw + F::TAB_F2 + ISW * F::EX_F2) + wave * N;
-    float *nrmTab = ring + (ISW - wave) * N;
-    for (int i = threadIdx.x; i < N; i += ISW * 64) win1[i] = a.win1[i];
-    for (int i = threadIdx.x; i < F::TAB_F2; i += ISW * 64) tabTw[i] = v2{tab[i].x, tab[i].y};
-    for (int t = threadIdx.x; t < a.hop; t += ISW * 64) {
-        float sum = 0.f;
-        for (int k = t + ((N - 1 - t) / a.hop) * a.hop; k >= 0; k -= a.hop) sum += win2[k];
-        nrmTab[t] = sum;
-    }
-    __syncthreads();
-
-    const long long run = (long long)blockIdx.x * ISW + wave;
-    if (run >= (long long)a.batch * runsPerClip) return;
-    const int b = (int)(run / runsPerClip), T = a.timeLength, H = a.hop;
-    const int f0 = (int)(run - (long long)b * runsPerClip) * framesPerRun;
-    const int f1 = f0 + framesPerRun < T ? f0 + framesPerRun : T;
-    const int halo = (N - 1) / H;
-    const int fs = f0 > halo ? f0 - halo : 0;
-    const long long outLen = (long long)(T - 1) * H + N;
-    const long long ownLo = (long long)f0 * H, ownHi = f1 == T ? outLen : (long long)f1 * H;
-    float *out = a.out + (long long)b * a.outStride;
-    const float scale = 0.5f / (float)N;
+    typedef typename F::B V;
+    constexpr int N = F::N, NR = F::NR;
+    OlaRing<N, ISW, F::TAB_F2, F::EX_F2> ola;
+    if (!ola.begin(smem_raw, a, tab, framesPerRun, runsPerClip)) return;
+    const int lane = ola.lane;
     const bool lane0 = lane == 0;
-    auto entering = [&](long long j) { return (j >= ownLo && j < ownHi) ? out[j] : 0.f; };
-    for (int t = lane; t < N; t += 64) ring[((long long)fs * H + t) & (N - 1)] = entering((long long)fs * H + t);
     v2 r[NR], m[NR];
     auto fetch = [&](int i) {
-        const v2 *re2 = reinterpret_cast<const v2 *>(a.re + ((long long)b * T + i) * N);
-        const v2 *im2 = reinterpret_cast<const v2 *>(a.im + ((long long)b * T + i) * N);
+        const v2 *re2 = reinterpret_cast<const v2 *>(a.re + ((long long)ola.b * ola.T + i) * N);
+        const v2 *im2 = reinterpret_cast<const v2 *>(a.im + ((long long)ola.b * ola.T + i) * N);
 #pragma unroll
         for (int q = 0; q < NR; ++q) {
             r[q] = re2[64 * q + lane];
             m[q] = im2[64 * q + lane];
         }
     };
-    fetch(fs);
-    for (int i = fs; i < f1; ++i) {
-        const long long j0 = (long long)i * H;
+    fetch(ola.fs);
+    for (int i = ola.fs; i < ola.f1; ++i) {
+        ola.at_frame(i);
         v2 v[NR];
 #pragma unroll
         for (int q = 0; q < NR; ++q) {
@@ -451,63 +405,16 @@ __global__ __launch_bounds__(ISW * 64) void k_istft_wsmall(AfxIstftArgs a, const
             }
             v[q] = v2{(r[q].x + rx) + (m[q].x - mx), (r[q].y + ry) + (m[q].y - my)};
         }
-        if (i + 1 < f1) fetch(i + 1);
-        typename F::B bn;
-        F::rfft(v, ex, tabTw, lane, bn);
-        int at[4 * NJ + 2];
-        float val[4 * NJ + 2];
-        bool ok[4 * NJ + 2];
-        auto put = [&](int e, bool valid, int n, float x) {
-            ok[e] = valid;
-            at[e] = (int)((j0 + n) & (N - 1));
-            val[e] = valid ? (x * scale) * win1[n] : 0.f;
-        };
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int k = lane + 64 * j;
-            const v2 X = bn.x[j], Y = bn.y[j];  // U[k], conj(U[N / 2 - k])
-            put(4 * j, true, k, X.x + X.y);
-            put(4 * j + 1, k > 0, (N - k) & (N - 1), X.x - X.y);
-            put(4 * j + 2, true, N / 2 - k, Y.x - Y.y);
-            put(4 * j + 3, k > 0, (N / 2 + k) & (N - 1), Y.x + Y.y);
-        }
-        put(4 * NJ, lane0, N / 4, bn.xm.x + bn.xm.y);
-        put(4 * NJ + 1, lane0, 3 * N / 4, bn.xm.x - bn.xm.y);
-        float cur[4 * NJ + 2];
-#pragma unroll
-        for (int e = 0; e < 4 * NJ + 2; ++e) cur[e] = ok[e] ? ring[at[e]] : 0.f;
-#pragma unroll
-        for (int e = 0; e < 4 * NJ + 2; ++e)
-            if (ok[e]) ring[at[e]] = cur[e] + val[e];
-        wave_lds_order();
-        if (i >= f0) {
-            const int cnt = i == T - 1 ? N : H;
-            auto power = [&](long long j) {
-                if (j >= N && j / H <= T - 1) return nrmTab[(int)(j % H)];
-                long long iLo = j >= N ? (j - N) / H + 1 : 0, iHi = j / H;
-                if (iHi > T - 1) iHi = T - 1;
-                float nrm = 0.f;
-                for (long long q = iLo; q <= iHi; ++q) nrm += win2[(int)(j - q * H)];
-                return nrm;
-            };
-            for (int t0 = 0; t0 < cnt; t0 += 256) {
-                float acc[4], nrm[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int t = t0 + lane + 64 * u;
-                    acc[u] = t < cnt ? ring[(j0 + t) & (N - 1)] : 0.f;
-                    nrm[u] = t < cnt ? power(j0 + t) : 1.f;
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int t = t0 + lane + 64 * u;
-                    if (t < cnt) out[j0 + t] = acc[u] / (nrm[u] < 1e-6f ? 1.f : nrm[u]);
-                }
-            }
-        }
-        wave_lds_order();
-        if (i + 1 < f1)
-            for (int t = lane; t < H; t += 64) ring[(j0 + N + t) & (N - 1)] = entering(j0 + N + t);
+        if (i + 1 < ola.f1) fetch(i + 1);
+        V bn;
+        F::rfft(v, ola.ex, ola.tabTw, lane, bn);
+        OlaBatch<2 * V::SLOTS> bt;  // one batch per frame
+        bn.for_each([&](int slot, v2 Z) {
+            const bool owned = V::owned(slot, lane);
+            ola.template add_bin<V::SLOTS>(bt, slot, owned, owned && V::paired(slot, lane), V::bin(slot, lane), V::mirrored(slot), Z);
+        });
+        ola.template drain<4>();
+        ola.enter_next();
     }
 }
 
@@ -519,76 +426,24 @@ __global__ __launch_bounds__(ISW * 64) void k_istft_w256(AfxIstftArgs a, const f
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     typedef afxws::Fft512 F;
     constexpr int N = 256;
-    float *win1 = reinterpret_cast<float *>(smem_raw);
-    const float *__restrict__ win2 = a.win2;
-    v2 *tabTw = reinterpret_cast<v2 *>(win1 + N);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    v2 *ex = tabTw + F::TAB_F2 + wave * F::EX_F2;
-    float *ring = reinterpret_cast<float *>(tabTw + F::TAB_F2 + ISW * F::EX_F2) + wave * N;
-    float *nrmTab = ring + (ISW - wave) * N;
-    for (int i = threadIdx.x; i < N; i += ISW * 64) win1[i] = a.win1[i];
-    for (int i = threadIdx.x; i < F::TAB_F2; i += ISW * 64) tabTw[i] = v2{tab[i].x, tab[i].y};
-    for (int t = threadIdx.x; t < a.hop; t += ISW * 64) {
-        float sum = 0.f;
-        for (int k = t + ((N - 1 - t) / a.hop) * a.hop; k >= 0; k -= a.hop) sum += win2[k];
-        nrmTab[t] = sum;
-    }
-    __syncthreads();
-
-    const long long run = (long long)blockIdx.x * ISW + wave;
-    if (run >= (long long)a.batch * runsPerClip) return;
-    const int b = (int)(run / runsPerClip), T = a.timeLength, H = a.hop;
-    const int f0 = (int)(run - (long long)b * runsPerClip) * framesPerRun;
-    const int f1 = f0 + framesPerRun < T ? f0 + framesPerRun : T;
-    const int halo = (N - 1) / H;
-    const int fs = f0 > halo ? f0 - halo : 0;
-    const long long outLen = (long long)(T - 1) * H + N;
-    const long long ownLo = (long long)f0 * H, ownHi = f1 == T ? outLen : (long long)f1 * H;
-    float *out = a.out + (long long)b * a.outStride;
-    const float scale = 0.5f / (float)N;
+    OlaRing<N, ISW, F::TAB_F2, F::EX_F2> ola;
+    if (!ola.begin(smem_raw, a, tab, framesPerRun, runsPerClip)) return;
+    const int lane = ola.lane, b = ola.b, T = ola.T;
     const bool lane0 = lane == 0;
-    auto entering = [&](long long j) { return (j >= ownLo && j < ownHi) ? out[j] : 0.f; };
-    for (int t = lane; t < N; t += 64) ring[((long long)fs * H + t) & (N - 1)] = entering((long long)fs * H + t);
-    auto power = [&](long long j) {
-        if (j >= N && j / H <= T - 1) return nrmTab[(int)(j % H)];
-        long long iLo = j >= N ? (j - N) / H + 1 : 0, iHi = j / H;
-        if (iHi > T - 1) iHi = T - 1;
-        float nrm = 0.f;
-        for (long long q = iLo; q <= iHi; ++q) nrm += win2[(int)(j - q * H)];
-        return nrm;
-    };
     // one frame's samples (x[q] = sample lane + 64 q) into the ring, its finished samples out, the next frame's new samples in
     auto overlap_add = [&](int i, const float (&x)[4]) {
-        const long long j0 = (long long)i * H;
-        float cur[4];
+        ola.at_frame(i);
+        OlaBatch<4> bt;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) cur[q] = ring[(j0 + lane + 64 * q) & (N - 1)];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) ring[(j0 + lane + 64 * q) & (N - 1)] = cur[q] + (x[q] * scale) * win1[lane + 64 * q];
-        wave_lds_order();
-        if (i >= f0) {
-            const int cnt = i == T - 1 ? N : H;
-            float acc[4], nrm[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int t = lane + 64 * u;
-                acc[u] = t < cnt ? ring[(j0 + t) & (N - 1)] : 0.f;
-                nrm[u] = t < cnt ? power(j0 + t) : 1.f;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int t = lane + 64 * u;
-                if (t < cnt) out[j0 + t] = acc[u] / (nrm[u] < 1e-6f ? 1.f : nrm[u]);
-            }
-        }
-        wave_lds_order();
-        if (i + 1 < f1)
-            for (int t = lane; t < H; t += 64) ring[(j0 + N + t) & (N - 1)] = entering(j0 + N + t);
+        for (int q = 0; q < 4; ++q) ola.put(bt, q, true, lane + 64 * q, x[q]);
+        ola.flush(bt);
+        ola.drain<4>();
+        ola.enter_next();
         wave_lds_order();
     };
 
-    for (int i = fs; i < f1; i += 2) {
-        const int ib = i + 1 < f1 ? i + 1 : i;  // an odd run: the last frame rides twice, added once
+    for (int i = ola.fs; i < ola.f1; i += 2) {
+        const int ib = i + 1 < ola.f1 ? i + 1 : i;  // an odd run: the last frame rides twice, added once
         const float *ra = a.re + ((long long)b * T + i) * N, *ia = a.im + ((long long)b * T + i) * N;
         const float *rb = a.re + ((long long)b * T + ib) * N, *ib_ = a.im + ((long long)b * T + ib) * N;
         float are[4], aim[4], bre[4], bim[4];
@@ -615,7 +470,7 @@ __global__ __launch_bounds__(ISW * 64) void k_istft_w256(AfxIstftArgs a, const f
             const float asr = are[r] + mar, asi = aim[r] - mai, bsr = bre[r] + mbr, bsi = bim[r] - mbi;  // 2 x the Hermitian parts
             v[r] = v2{asr - bsi, -asi - bsr};
         }
-        F::cfft(v, ex, tabTw, lane);
+        F::cfft(v, ola.ex, ola.tabTw, lane);
         __builtin_amdgcn_s_setprio(0);
         wave_lds_order();  // (the natural-order image in `ex` is not needed: the lanes' registers hold their samples)
         float xa[4], xb[4];
@@ -657,88 +512,76 @@ int resident_groups(size_t lds, int waves) {
     return g < 1 ? 1 : (int)g;
 }
 
+}  // namespace
+
+extern "C" const void *afxk_wave_tables(void);  // afx_stft.hip: the afxw tables + the W_4096^k tail
+
+namespace {
+
 // twiddle tables of the small wave transforms, one device copy per device and size (never freed)
 template <class F>
 const float2 *small_tables() {
     return reinterpret_cast<const float2 *>(afx_device_table<F::fill_tables>(sizeof(float) * 2 * F::TAB_F2));
 }
+const float2 *wave_tables() { return static_cast<const float2 *>(afxk_wave_tables()); }
 
-template <class F>
-int launch_istft_small(const AfxIstftArgs *a, void *stream) {
-    const float2 *tab = small_tables<F>();
+// One row per n_fft of the one-launch inverse.  The sizes were written one by one (round 6) and differ in more than their
+// geometry; every difference is kept as it was and stands here as a field, to be read side by side.
+struct IstftSize {
+    void (*kernel)(AfxIstftArgs, const float2 *, int, int);
+    const char *name;
+    int N, waves;            // frame length; waves per workgroup
+    int tabF2, exF2;         // float2 of twiddle tables in the LDS; of one wave's exchange image
+    const float2 *(*tables)();
+    unsigned align;          // bytes the re / im planes must be aligned to (the lanes' vector loads)
+    bool residentGroups;     // the wave slots that place the runs count the workgroups a CU holds at a time (else one per CU)
+    int least;               // shortest run of frames
+    bool ldsLimit;           // the hop's window-power sums can push the LDS past 160 KB: then not this kernel's case
+    bool dynLdsAttribute;    // raise the kernel's dynamic-LDS limit before the launch
+};
+const IstftSize ISTFT_256 = {k_istft_w256, "k_istft_w256", 256, ISW, afxws::Fft512::TAB_F2, afxws::Fft512::EX_F2, small_tables<afxws::Fft512>,
+                             8, true, 32, false, false};
+const IstftSize ISTFT_512 = {k_istft_wsmall<afxws::Fft512>, "k_istft_wsmall", 512, ISW, afxws::Fft512::TAB_F2, afxws::Fft512::EX_F2,
+                             small_tables<afxws::Fft512>, 8, true, 16, false, true};
+const IstftSize ISTFT_1024 = {k_istft_wsmall<afxws::Fft1k>, "k_istft_wsmall", 1024, ISW, afxws::Fft1k::TAB_F2, afxws::Fft1k::EX_F2,
+                              small_tables<afxws::Fft1k>, 8, true, 16, false, true};
+const IstftSize ISTFT_2048 = {k_istft_w2048, "k_istft_w2048", 2048, IW, afxw::TAB_F2, afxw::EX_F2, wave_tables, 8, false, 16, false, true};
+const IstftSize ISTFT_4096 = {k_istft_w4096, "k_istft_w4096", 4096, IW4, afxw::TAB_F2 + afxw::W4_PAD_F2, afxw::EX_F2, wave_tables,
+                              16, false, 16, true, true};  // (hops beyond ~3000 miss the LDS limit: the size-generic launches)
+
+// CU count -> LDS bytes (OlaRing's layout) -> frames per run -> grid -> attribute -> launch
+int launch_istft(const IstftSize &z, const AfxIstftArgs *a, void *stream) {
+    if ((reinterpret_cast<uintptr_t>(a->re) | reinterpret_cast<uintptr_t>(a->im)) & (z.align - 1)) return AFX_ERR_UNSUPPORTED;
+    const float2 *tab = z.tables();
     if (!tab) return AFX_ERR_UNSUPPORTED;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const size_t lds = sizeof(float) * F::N + sizeof(float2) * (size_t)(F::TAB_F2 + ISW * F::EX_F2) + sizeof(float) * F::N * ISW +
+    const size_t lds = sizeof(float) * z.N + sizeof(float2) * (size_t)(z.tabF2 + z.waves * z.exF2) + sizeof(float) * z.N * z.waves +
                        sizeof(float) * (size_t)a->hop;
-    const long long fpr = frames_per_run(a->batch, a->timeLength, (long long)cus * ISW * resident_groups(lds, ISW), (F::N - 1) / a->hop, 16);
+    if (z.ldsLimit && lds > 160 * 1024) return AFX_ERR_UNSUPPORTED;
+    const long long slots = (long long)afx_cu_count() * z.waves * (z.residentGroups ? resident_groups(lds, z.waves) : 1);
+    const long long fpr = frames_per_run(a->batch, a->timeLength, slots, (z.N - 1) / a->hop, z.least);
     const long long runsPerClip = (a->timeLength + fpr - 1) / fpr, runs = runsPerClip * a->batch;
-    const long long blocks = (runs + ISW - 1) / ISW;
+    const long long blocks = (runs + z.waves - 1) / z.waves;
     if (blocks > 0x7fffffffLL) return AFX_ERR_UNSUPPORTED;
-    AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_istft_wsmall<F>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_istft_wsmall<F>, dim3((unsigned)blocks), dim3(ISW * 64), lds, (hipStream_t)stream, *a, tab, (int)fpr, (int)runsPerClip);
-    AFX_LAUNCH_CHECK("k_istft_wsmall");
+    if (z.dynLdsAttribute)
+        AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(z.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(z.kernel, dim3((unsigned)blocks), dim3(z.waves * 64), lds, (hipStream_t)stream, *a, tab, (int)fpr, (int)runsPerClip);
+    AFX_LAUNCH_CHECK(z.name);
     return AFX_OK;
 }
 
 }  // namespace
 
-extern "C" const void *afxk_wave_tables(void);  // afx_stft.hip
-
 // AFX_ERR_UNSUPPORTED: not this kernel's case (afxk_istft then runs the two size-generic launches, which need a->frames)
 extern "C" int afxk_istft_fused(const AfxIstftArgs *a, void *stream) {
-    if (a->hop < 1 || a->hop > (1 << a->radix2Exp) || a->timeLength < 1 || (reinterpret_cast<uintptr_t>(a->re) & 7) ||
-        (reinterpret_cast<uintptr_t>(a->im) & 7))
-        return AFX_ERR_UNSUPPORTED;
-    if (a->radix2Exp == 12) {
-        const float2 *tab4 = static_cast<const float2 *>(afxk_wave_tables());
-        if (!tab4 || (reinterpret_cast<uintptr_t>(a->re) & 15) || (reinterpret_cast<uintptr_t>(a->im) & 15)) return AFX_ERR_UNSUPPORTED;
-        int dev4 = 0, cus4 = 256;
-        if (hipGetDevice(&dev4) == hipSuccess) (void)hipDeviceGetAttribute(&cus4, hipDeviceAttributeMultiprocessorCount, dev4);
-        const long long fpr4 = frames_per_run(a->batch, a->timeLength, (long long)cus4 * IW4, 4095 / a->hop, 16);
-        const long long rpc4 = (a->timeLength + fpr4 - 1) / fpr4, blocks4 = (rpc4 * a->batch + IW4 - 1) / IW4;
-        if (blocks4 > 0x7fffffffLL) return AFX_ERR_UNSUPPORTED;
-        const size_t lds4 = sizeof(float) * 4096 + sizeof(float2) * (size_t)(afxw::TAB_F2 + 1032 + IW4 * afxw::EX_F2) + sizeof(float) * 4096 * IW4 +
-                            sizeof(float) * (size_t)a->hop;
-        if (lds4 > 160 * 1024) return AFX_ERR_UNSUPPORTED;  // (hops beyond ~3000: the size-generic launches)
-        AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_istft_w4096), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4));
-        hipLaunchKernelGGL(k_istft_w4096, dim3((unsigned)blocks4), dim3(IW4 * 64), lds4, (hipStream_t)stream, *a, tab4, (int)fpr4, (int)rpc4);
-        AFX_LAUNCH_CHECK("k_istft_w4096");
-        return AFX_OK;
+    if (a->hop < 1 || a->hop > (1 << a->radix2Exp) || a->timeLength < 1) return AFX_ERR_UNSUPPORTED;
+    switch (a->radix2Exp) {
+        case 8: return launch_istft(ISTFT_256, a, stream);
+        case 9: return launch_istft(ISTFT_512, a, stream);
+        case 10: return launch_istft(ISTFT_1024, a, stream);
+        case 11: return launch_istft(ISTFT_2048, a, stream);
+        case 12: return launch_istft(ISTFT_4096, a, stream);
+        default: return AFX_ERR_UNSUPPORTED;
     }
-    if (a->radix2Exp == 10) return launch_istft_small<afxws::Fft1k>(a, stream);
-    if (a->radix2Exp == 9) return launch_istft_small<afxws::Fft512>(a, stream);
-    if (a->radix2Exp == 8) {
-        typedef afxws::Fft512 F8;
-        const float2 *tab8 = small_tables<F8>();
-        if (!tab8) return AFX_ERR_UNSUPPORTED;
-        int dev8 = 0, cus8 = 256;
-        if (hipGetDevice(&dev8) == hipSuccess) (void)hipDeviceGetAttribute(&cus8, hipDeviceAttributeMultiprocessorCount, dev8);
-        const size_t lds8 = sizeof(float) * 256 + sizeof(float2) * (size_t)(F8::TAB_F2 + ISW * F8::EX_F2) + sizeof(float) * 256 * ISW +
-                            sizeof(float) * (size_t)a->hop;
-        const long long fpr8 = frames_per_run(a->batch, a->timeLength, (long long)cus8 * ISW * resident_groups(lds8, ISW), 255 / a->hop, 32);
-        const long long rpc8 = (a->timeLength + fpr8 - 1) / fpr8, blocks8 = (rpc8 * a->batch + ISW - 1) / ISW;
-        if (blocks8 > 0x7fffffffLL) return AFX_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL(k_istft_w256, dim3((unsigned)blocks8), dim3(ISW * 64), lds8, (hipStream_t)stream, *a, tab8, (int)fpr8, (int)rpc8);
-        AFX_LAUNCH_CHECK("k_istft_w256");
-        return AFX_OK;
-    }
-    if (a->radix2Exp != 11) return AFX_ERR_UNSUPPORTED;
-    const float2 *tab = static_cast<const float2 *>(afxk_wave_tables());
-    if (!tab) return AFX_ERR_UNSUPPORTED;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    // runs of >= 32 frames (the frames before a run are transformed again for their tails: 3 at hop N / 4), two rounds of waves
-    const long long fpr = frames_per_run(a->batch, a->timeLength, (long long)cus * IW, 2047 / a->hop, 16);
-    const long long runsPerClip = (a->timeLength + fpr - 1) / fpr, runs = runsPerClip * a->batch;
-    const long long blocks = (runs + IW - 1) / IW;
-    if (blocks > 0x7fffffffLL) return AFX_ERR_UNSUPPORTED;
-    const size_t lds = sizeof(float) * 2048 + sizeof(float2) * (size_t)(afxw::TAB_F2 + IW * afxw::EX_F2) + sizeof(float) * 2048 * IW +
-                       sizeof(float) * (size_t)a->hop;
-    AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_istft_w2048), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_istft_w2048, dim3((unsigned)blocks), dim3(IW * 64), lds, (hipStream_t)stream, *a, tab, (int)fpr, (int)runsPerClip);
-    AFX_LAUNCH_CHECK("k_istft_w2048");
-    return AFX_OK;
 }
 
 extern "C" int afxk_istft(const AfxIstftArgs *a, void *stream) {

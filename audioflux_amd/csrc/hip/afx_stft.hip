@@ -171,13 +171,13 @@ __global__ __launch_bounds__(SW * 64) void k_stft_wave(AfxStftArgs a, const floa
                                                       int framesPerWave, int vecOk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int N = 1 << R2, M = N / 2;
-    constexpr int NTAB = afxw::TAB_F2 + (R2 == 12 ? 1032 : 0);
+    constexpr int NTAB = afxw::TAB_F2 + (R2 == 12 ? afxw::W4_PAD_F2 : 0);
     float *tabWin = reinterpret_cast<float *>(smem_raw);       // [N]
     v2 *tabTw = reinterpret_cast<v2 *>(tabWin + N);            // afxw tables (| W_4096^k)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     v2 *ex = tabTw + NTAB + wave * afxw::EX_F2;
     for (int i = threadIdx.x; i < N; i += SW * 64) tabWin[i] = a.window[i];
-    for (int i = threadIdx.x; i < afxw::TAB_F2 + (R2 == 12 ? 1025 : 0); i += SW * 64) tabTw[i] = v2{tab[i].x, tab[i].y};
+    for (int i = threadIdx.x; i < afxw::TAB_F2 + (R2 == 12 ? afxw::W4_F2 : 0); i += SW * 64) tabTw[i] = v2{tab[i].x, tab[i].y};
     __syncthreads();
     const afxw::Tables tb = {tabTw, tabTw + afxw::TAB_TW1_F2, tabTw + afxw::TAB_TW1_F2 + afxw::TAB_TW2_F2};
     const v2 *tabW4 = tabTw + afxw::TAB_F2;
@@ -345,7 +345,7 @@ const float2 *wave_tables() {
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
     std::lock_guard<std::mutex> lk(mu);
     if (!dTab[dev]) {
-        const size_t n = (size_t)afxw::TAB_F2 + 1025;
+        const size_t n = (size_t)afxw::TAB_F2 + afxw::W4_F2;
         float *h = static_cast<float *>(calloc(2 * n, sizeof(float)));
         if (!h) return nullptr;
         afxw::fill_tables(h);
@@ -366,7 +366,7 @@ const float2 *wave_tables() {
 
 }  // namespace
 
-// the wave kernels' twiddle tables (afxw::TAB_F2 float2 + 1025 of W_4096) for the other translation units (afx_istft.hip)
+// the wave kernels' twiddle tables (afxw::TAB_F2 float2 + afxw::W4_F2 of W_4096) for the other translation units (afx_istft.hip)
 extern "C" const void *afxk_wave_tables(void) { return wave_tables(); }
 
 namespace {
@@ -382,7 +382,7 @@ int launch_stft_wave(const AfxStftArgs *a, const float2 *tab, long long frames, 
     long long fpw = frames / (256LL * SW * 4);
     fpw = fpw < 1 ? 1 : (fpw > 16 ? 16 : fpw);
     const long long waves = (frames + fpw - 1) / fpw, blocks = (waves + SW - 1) / SW;
-    const size_t lds = sizeof(float) * N + sizeof(float2) * (size_t)(afxw::TAB_F2 + (R2 == 12 ? 1032 : 0) + SW * afxw::EX_F2);
+    const size_t lds = sizeof(float) * N + sizeof(float2) * (size_t)(afxw::TAB_F2 + (R2 == 12 ? afxw::W4_PAD_F2 : 0) + SW * afxw::EX_F2);
     AFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_stft_wave<R2, CPLX>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((k_stft_wave<R2, CPLX>), dim3((unsigned)blocks), dim3(SW * 64), lds, (hipStream_t)stream, *a, tab,

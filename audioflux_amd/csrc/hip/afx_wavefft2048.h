@@ -26,6 +26,9 @@ constexpr int TW2_ROW = 18;             // float2 per row: 16 + 2 (144 bytes, 16
 constexpr int TAB_TW2_F2 = 4 * TW2_ROW; // W_64^(m2 j1)       at [m2][j1]
 constexpr int TAB_TW3_F2 = 1024;        // 0.5 W_2048^k
 constexpr int TAB_F2 = TAB_TW1_F2 + TAB_TW2_F2 + TAB_TW3_F2;
+// n_fft 4096 appends W_4096^k, k <= 1024, to the tables: W4_F2 float2 are there to load, W4_PAD_F2 (a 16-byte multiple) are
+// reserved for them in the LDS
+constexpr int W4_F2 = 1025, W4_PAD_F2 = 1032;
 
 struct Tables {  // LDS-resident
     const v2 *tw1, *tw2, *tw3;
@@ -36,9 +39,43 @@ struct Tables {  // LDS-resident
 // xc[i] = S[128 + 256 i], yc[i] = conj(S[896 - 256 i]) in every lane (base 128 mirrors itself).
 // Lane 0, s = 0 holds k = 0, 256, 512, 768 with partners 1024, 768, 512, 256 (bins 256, 512, 768
 // therefore appear twice, equal up to rounding).
+//
+// The same registers as 20 SLOTS, one bin each, pair by pair: slot 8 s + 2 j is x[s][j], 8 s + 2 j + 1 is y[s][j], 16 + 2 i is
+// xc[i], 17 + 2 i is yc[i].  A consumer asks the view which bin a slot is instead of deriving it; for_each() hands out the
+// registers as they are: S[bin], conjugated where mirrored(slot).
 struct Bins {
     v2 x[2][4], y[2][4];
     v2 xc[2], yc[2];
+
+    static constexpr int SLOTS = 20;
+    // the k' of pair p of the layout: lane + 64 s + 256 j for p = 4 s + j < 8, the base-128 extras 128 + 256 i for p = 8 + i
+    static __device__ __forceinline__ int base(int p, int lane) { return p < 8 ? lane + 64 * (p >> 2) + 256 * (p & 3) : 128 + 256 * (p - 8); }
+    // position: the k' a slot belongs to; mirrored: it is the y of the pair, conj(S[1024 - k'])
+    static __device__ __forceinline__ int position(int slot, int lane) { return base(slot >> 1, lane); }
+    static __device__ __forceinline__ bool mirrored(int slot) { return slot & 1; }
+    static __device__ __forceinline__ int bin(int slot, int lane) { return mirrored(slot) ? 1024 - position(slot, lane) : position(slot, lane); }
+    // held: the lane's registers are the (or a) copy of the bin to use -- the extras are in every lane, lane 0 speaks for them
+    static __device__ __forceinline__ bool held(int slot, int lane) { return slot < 16 || lane == 0; }
+    // paired: the bin has a mirror image N - bin in a real sequence's transform (not bins 0 and 1024: k' = 0)
+    static __device__ __forceinline__ bool paired(int slot, int lane) { return position(slot, lane) > 0; }
+    // owned: held, and every bin exactly once: of bins 256, 512, 768 lane 0 owns the x copy, not y[0][3 .. 1] (slots 7, 5, 3)
+    static __device__ __forceinline__ bool owned(int slot, int lane) { return slot < 16 ? !(lane == 0 && slot < 8 && slot > 1 && (slot & 1)) : lane == 0; }
+
+    template <typename F>
+    __device__ __forceinline__ void for_each(F f) const {  // f(slot, register), slots ascending, slot a constant after unrolling
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                f(8 * s + 2 * j, x[s][j]);
+                f(8 * s + 2 * j + 1, y[s][j]);
+            }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            f(16 + 2 * i, xc[i]);
+            f(17 + 2 * i, yc[i]);
+        }
+    }
 };
 
 __device__ __forceinline__ void split(v2 A, v2 B, v2 w /* 0.5 W_2048^k */, v2 &x, v2 &y) {
@@ -127,17 +164,35 @@ __device__ __forceinline__ void combine4096(const Bins &e, const Bins &o, const 
     for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            position(4 * (4 * s + j), lane + 64 * s + 256 * j, e.x[s][j], o.x[s][j], e.y[s][j], o.y[s][j]);
+            position(4 * (4 * s + j), Bins::base(4 * s + j, lane), e.x[s][j], o.x[s][j], e.y[s][j], o.y[s][j]);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) position(32 + 4 * i, 128 + 256 * i, e.xc[i], o.xc[i], e.yc[i], o.yc[i]);
+    for (int i = 0; i < 2; ++i) position(32 + 4 * i, Bins::base(8 + i, lane), e.xc[i], o.xc[i], e.yc[i], o.yc[i]);
 }
 
 // bin index of a slot of combine4096 for this lane
 __device__ __forceinline__ int bin4096(int slot, int lane) {
-    const int p = slot >> 2, r = slot & 3;
-    const int kp = p < 8 ? lane + 64 * (p >> 2) + 256 * (p & 3) : 128 + 256 * (p - 8);
+    const int kp = Bins::base(slot >> 2, lane), r = slot & 3;
     return r == 0 ? kp : r == 1 ? 2048 - kp : r == 2 ? 1024 - kp : 1024 + kp;
 }
+
+// the slot view of the 4096 layout (see Bins): 40 slots of a pair of transforms
+struct Bins4096 {
+    static constexpr int SLOTS = 40;
+    static __device__ __forceinline__ int position(int slot, int lane) { return Bins::base(slot >> 2, lane); }  // k' of the slot
+    static __device__ __forceinline__ int bin(int slot, int lane) { return bin4096(slot, lane); }
+    static __device__ __forceinline__ bool held(int slot, int lane) { return slot < 32 || lane == 0; }
+    // lane 0 at p = 1 .. 3 holds k' = 256, 512, 768, whose partners 1024 -+ k' are its own slots of 4 - p; at k' = 0 bin 1024 comes
+    // out twice (1024 - 0, 1024 + 0)
+    static __device__ __forceinline__ bool owned(int slot, int lane) {
+        const int p = slot >> 2, r = slot & 3;
+        if (p >= 8) return lane == 0;
+        return !(lane == 0 && ((p > 0 && p < 4 && r >= 2) || (p == 0 && r == 3)));
+    }
+    template <typename F>
+    static __device__ __forceinline__ void for_each(const Bins &e, const Bins &o, const v2 *w4, int lane, F f) {
+        combine4096(e, o, w4, lane, f);
+    }
+};
 
 // host: the three twiddle tables, evaluated in double and rounded once; tab[2 * TAB_F2] floats
 inline void fill_tables(float *tab) {

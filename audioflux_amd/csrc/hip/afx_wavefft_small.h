@@ -23,9 +23,28 @@ __device__ __forceinline__ void split(v2 A, v2 B, v2 w, v2 &x, v2 &y) {
 
 // Spectrum of the wave's sequence, spread over the lanes: for j < NJ and k = lane + 64 j: x[j] = S[k], y[j] =
 // conj(S[N/2 - k]) (lane 0, j = 0: S[0] and conj(S[N/2])); xm = S[N/4] in every lane.  Every bin 0 .. N/2 exactly once.
+// As 2 NJ + 1 SLOTS, one bin each (the view of afxw::Bins), pair by pair: slot 2 j is x[j], 2 j + 1 is y[j], 2 NJ is xm.
 template <int NJ>
 struct Bins {
     v2 x[NJ], y[NJ], xm;
+
+    static constexpr int SLOTS = 2 * NJ + 1, M = 128 * NJ;  // M = N / 2
+    static __device__ __forceinline__ int position(int slot, int lane) { return slot < 2 * NJ ? lane + 64 * (slot >> 1) : M / 2; }
+    static __device__ __forceinline__ bool mirrored(int slot) { return slot < 2 * NJ && (slot & 1); }  // a y slot: conj(S[M - k])
+    static __device__ __forceinline__ int bin(int slot, int lane) { return mirrored(slot) ? M - position(slot, lane) : position(slot, lane); }
+    static __device__ __forceinline__ bool paired(int slot, int lane) { return position(slot, lane) > 0; }  // not bins 0 and M (k = 0)
+    static __device__ __forceinline__ bool held(int slot, int lane) { return slot < 2 * NJ || lane == 0; }  // xm is in every lane
+    static __device__ __forceinline__ bool owned(int slot, int lane) { return held(slot, lane); }          // no bin twice
+
+    template <typename F>
+    __device__ __forceinline__ void for_each(F f) const {  // f(slot, register), slots ascending, slot a constant after unrolling
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            f(2 * j, x[j]);
+            f(2 * j + 1, y[j]);
+        }
+        f(2 * NJ, xm);
+    }
 };
 
 // ---- N = 1024: 512 complex points, 8 x 8 x 8 ------------------------------------------------------------------------
