@@ -483,7 +483,11 @@ int afxk_melfused_kind(const void *plan);
  * of workgroups is full -- 1 / 2 / 3 rounds measure the same at the headline size (1.558 / 1.559 / 1.559 ms per step), 6
  * rounds + 1.2 %, two keep the tail short.  A call that cannot fill one round with 16-frame runs -- the one-clip legacy
  * entry points: 1000 frames -- is spread over all CUs instead (16 frames in sequence per wave were 75 us of a 1000-frame
- * call's 190, profiles/r05_legacy_phases.txt).  Shared with the host tests (tests/test_bandplan.py). */
+ * call's 190, profiles/r05_legacy_phases.txt).  Shared with the host tests (tests/test_bandplan.py).
+ * n_fft 2048 (afx_melfused2.hip, round 7) takes only the workgroups' ranges from here -- workgroup b owns the frames
+ * [b, b + 1) x wavesPerWg x *framesPerWave -- in ONE round: inside a range no wave owns a share, the waves claim runs of frames
+ * from a counter in LDS, so that none of the twelve leaves its SIMD long before the others (profiles/r07_ab_headline.txt).  The
+ * kernels of n_fft 512, 1024 and 4096 keep the fixed share per wave. */
 static inline long long afx_frame_split(long long total, int cus, int wavesPerWg, int rounds, long long *framesPerWave) {
     *framesPerWave = 0;
     if (total <= 0) return 0;

@@ -49,6 +49,13 @@
 #ifndef AFX_V2_CCEVERY
 #define AFX_V2_CCEVERY 16
 #endif
+// measurement switches of round 7 (profiles/r07_ab_headline.txt): AFX_V2_STAMPS -- every wave records s_memtime at its first frame, at
+// every 16th frame and after its last one, with its workgroup, wave index, frame count and hardware id, in a debug buffer of its own
+// that the launcher writes to the file AFX_V2_STAMPS_FILE names (tools/v2_stamps.py reads it)
+#ifdef AFX_V2_STAMPS
+#include <cstdio>
+#include <vector>
+#endif
 
 namespace {
 
@@ -61,6 +68,7 @@ constexpr int P1 = 72;                       // float2 per row of the exchange-1
 constexpr int PROW_OFF = 5120;               // byte offset of the power row in a wave's region
 constexpr int PROW_F = 1104;                 // 1025 bins + zero pad for the fixed-length band loops
 constexpr int WAVE_LDS = PROW_OFF + PROW_F * 4;  // 9536: pad [9220, 9536) lies behind both images
+constexpr int CLAIM_LDS = 16;                // behind the waves' regions: the workgroup's claim counter (one word)
 static_assert(16 * P1 * 8 <= PROW_OFF + 1025 * 4, "exchange image must end before the zero pad");
 // table blob, byte offsets (built on the host by fill_tables + afxk_melfused_create, copied to LDS per workgroup)
 constexpr int T_WIN = 0;                     // [8][64] float4: (w[2n], w[2n+1]) of rows n1 = 2j, 2j + 1
@@ -74,7 +82,16 @@ __host__ __device__ constexpr int wpitch(int ta, int tb) { return ta + tb + 4; }
 __host__ __device__ constexpr int tab_bytes(int ta, int tb) { return T_BAND + 64 * wpitch(ta, tb) * 4; }
 constexpr int DCT_PITCH = 36;                // floats per lane of the DCT operand table (9 x 16 B: conflict-free b128)
 __host__ __device__ constexpr int block_lds_bytes(int ta, int tb, bool cc) {
-    return tab_bytes(ta, tb) + (cc ? 64 * DCT_PITCH * 4 : 0) + WAVES * WAVE_LDS;  // (complex results: fewer waves, less)
+    return tab_bytes(ta, tb) + (cc ? 64 * DCT_PITCH * 4 : 0) + WAVES * WAVE_LDS + CLAIM_LDS;  // (complex results: fewer waves, less)
+}
+
+// Frames of a workgroup's range that one claim takes when `left` remain (guided: about left / (2 waves)): whole 16-frame cepstrum
+// blocks while every wave can still have one, then multiples of 4 down to `minRun`, so that the waves of a workgroup end within a few
+// frame times of each other
+__host__ __device__ constexpr int claim_length(int left, int waves, int minRun) {
+    const int g = left / (2 * waves);
+    if (left >= 16 * waves) return g >= 16 ? g & ~15 : 16;
+    return (g & ~3) > minRun ? g & ~3 : minRun;
 }
 
 struct KArgs2 {
@@ -82,7 +99,7 @@ struct KArgs2 {
     long long clipStride;
     long long totalFrames;
     int timeLength, hop;
-    int framesPerWave;
+    long long framesPerWg; // workgroup b owns frames [b framesPerWg, (b + 1) framesPerWg) (< 2^30); its waves claim runs of them
     int aligned;           // frame starts are 8-byte aligned -> float2 loads
     const float4 *tab;     // table blob
     const int *meta;       // [6][64]: startA, startB, rowA, rowB, segIdx lo / hi
@@ -102,7 +119,13 @@ struct KArgs2 {
     int binLo, binCount;
     long long outPitch;
     int vecOut;            // binLo == 0, all 1025 bins, 16-byte aligned rows of >= 1028 floats: 16-byte stores (the pad gets zeros)
+#ifdef AFX_V2_STAMPS
+    unsigned long long *stamps;  // [workgroups * waves][STAMP_WORDS]
+#endif
 };
+#ifdef AFX_V2_STAMPS
+constexpr int STAMP_WORDS = 64, STAMP_HEAD = 8;  // t0, t1, workgroup | wave << 32, frames, HW_ID, XCC_ID, -, -, then a stamp per 16 frames
+#endif
 
 // (lds_addr, RD64 / RD128, WR2_64, WR2ST_32, PIN, LDS_WAIT_N and the L1-bypassing load: afx_asm.h; wave_lds_sync, split_pair,
 // split_pair_c, cplx_map, lo2 / hi2: afx_melparts.h)
@@ -178,6 +201,7 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
             }
         }
         for (int i = 1025 + lane; i < PROW_F; i += 64) prow[i] = 0.f;  // zero pad, never overwritten
+        if (threadIdx.x == 0) *reinterpret_cast<int *>(smem + TABB + DCTB + NWV * WAVE_LDS) = 0;  // frames of the range claimed so far
     }
     __syncthreads();
 
@@ -208,14 +232,51 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
     const unsigned apa = R + 4 * startA, apb = R + 4 * startB;
     const unsigned awr = T0 + T_BAND + 4 * WP * lane;
 
-    const long long gw = (long long)blockIdx.x * NWV + wave;
-    long long f = gw * a.framesPerWave;
-    long long fEnd = f + a.framesPerWave;
-    if (fEnd > a.totalFrames) fEnd = a.totalFrames;
-    if (f >= fEnd) return;
-    int clip = (int)(f / a.timeLength);
-    int t = (int)(f - (long long)clip * a.timeLength);
-    int ccN = 0;  // frames of this wave whose cepstra are still to be formed
+    // ---- frame runs: no wave owns a share of the workgroup's range [wgBeg, wgBeg + wgN) -- a wave that runs out of frames claims
+    //      the next run from the counter in LDS (lane 0: fetch-add; the length from a read just before it, which may be stale:
+    //      runs never overlap, they are only a little longer than the guide asks for), and leaves when the range is used up.
+    //      A frame's values do not depend on the wave that computes it.  minRun: a range shorter than 4 frames per wave (small
+    //      launches: one round of workgroups cannot be filled) is still spread over all waves
+    const long long wgBeg = (long long)blockIdx.x * a.framesPerWg;
+    const int wgN = (int)(a.totalFrames - wgBeg < a.framesPerWg ? a.totalFrames - wgBeg : a.framesPerWg);
+    const int minRun = wgN >= 4 * NWV ? 4 : wgN > NWV ? (wgN + NWV - 1) / NWV : 1;
+    int *claimed = reinterpret_cast<int *>(smem + TABB + DCTB + NWV * WAVE_LDS);
+    // a run's clip and frame index (locate) come from its 32-bit offset in the range and the range's own clip and frame index: one
+    // 64-bit divide per wave, before the frame loop
+    const int wgClip = (int)(wgBeg / a.timeLength);
+    const unsigned wgT = (unsigned)(wgBeg - (long long)wgClip * a.timeLength);
+    auto locate = [&](long long fr, int &c, int &tt) {
+        const unsigned at = wgT + (unsigned)(fr - wgBeg);  // < 2^31 + 2^30
+        c = wgClip + (int)(at / (unsigned)a.timeLength);
+        tt = (int)(at % (unsigned)a.timeLength);
+    };
+    auto claim = [&](long long &rb, long long &re) -> bool {
+        int s = wgN, l = 0;
+        if (lane0) {
+            const int left = wgN - __atomic_load_n(claimed, __ATOMIC_RELAXED);
+            if (left > 0) {
+                l = claim_length(left, NWV, minRun);
+                s = __atomic_fetch_add(claimed, l, __ATOMIC_RELAXED);
+            }
+        }
+        s = __builtin_amdgcn_readfirstlane(s);
+        l = __builtin_amdgcn_readfirstlane(l);
+        if (s >= wgN) return false;
+        rb = wgBeg + s;
+        re = wgBeg + (s + l < wgN ? s + l : wgN);
+        return true;
+    };
+    int ccN = 0;  // frames of this run whose cepstra are still to be formed
+#ifdef AFX_V2_STAMPS
+    unsigned long long *stamp = a.stamps + ((long long)blockIdx.x * NWV + wave) * STAMP_WORDS;
+    int stampN = 0;  // frames done
+    if (lane0) {
+        stamp[0] = __builtin_amdgcn_s_memtime();
+        stamp[2] = (unsigned long long)blockIdx.x | ((unsigned long long)wave << 32);
+        stamp[4] = (unsigned)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));   // HW_REG_HW_ID, all 32 bits
+        stamp[5] = (unsigned)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11));  // HW_REG_XCC_ID
+    }
+#endif
 
     // raw samples of the frame about to be transformed: raw[n1] = (x[2n], x[2n+1]), n = 64 n1 + lane
     v2 raw[16];
@@ -234,7 +295,6 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
                 }
         }
     };
-    fetch(a.x + (long long)clip * a.clipStride + (long long)t * a.hop, 0);
 
     // ---- cepstra of `cnt` (<= 16) consecutive rows fb.. of this wave: C[16 frames, 16 coefficients] =
     //      log10(max(rows, 1e-8)) . D^T with v_mfma_f32_16x16x4_f32.  Lane (fi = lane & 15, g = lane >> 4)
@@ -292,6 +352,21 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
         ccN -= cnt;
     };
 
+    // one run after the other; between two runs every LDS operation of the wave has returned and the claim's own are waited for at
+    // once, so the hand-counted waits of the frame loop see the counts they always saw.  The frame loop itself is the loop of a
+    // fixed share, and f is kept per lane in it (laneZero) as it was when it came from the wave's index: with f in scalar
+    // registers, or with the next run's first frame fetched from inside this loop (one frame ahead, like every other frame), the
+    // compiler kept two or three register images of the overlapping frames, moved one onto the other once per frame and spilled
+    // 40-140 bytes per lane in every SHIFT > 0 instantiation.  So a run's first frame is fetched in the open, once per run
+    long long fClaim, fEndClaim;
+    while (claim(fClaim, fEndClaim)) {
+    int laneZero = 0;
+    PIN(laneZero);
+    long long f = fClaim + laneZero;
+    const long long fEnd = fEndClaim;
+    int clip, t;
+    locate(fClaim, clip, t);
+    fetch(a.x + (long long)clip * a.clipStride + (long long)t * a.hop, 0);
     for (; f < fEnd; ++f) {
         v2 v[16];
         MEL_PHASE(0);
@@ -592,11 +667,22 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
 
         }  // pass
 
+#ifdef AFX_V2_STAMPS
+        ++stampN;
+        if (lane0 && (stampN & 15) == 0 && STAMP_HEAD + (stampN >> 4) <= STAMP_WORDS) stamp[STAMP_HEAD - 1 + (stampN >> 4)] = __builtin_amdgcn_s_memtime();
+#endif
         if (++t == a.timeLength) {
             t = 0;
             ++clip;
         }
     }
+    }  // runs
+#ifdef AFX_V2_STAMPS
+    if (lane0) {
+        stamp[1] = __builtin_amdgcn_s_memtime();
+        stamp[3] = (unsigned long long)stampN;
+    }
+#endif
 }
 
 // window (hWindow != nullptr) and twiddle tables of the blob, byte offsets T_WIN / T_TW1 / T_TW2 / T_TW3
@@ -637,13 +723,53 @@ void fill_tables(float *tab, const float *hWindow) {
 
 constexpr AfxMelVariant kVariants[] = {{48, 16}, {72, 32}};
 
+// Workgroups of a launch and the frames each owns: afx_frame_split's shape (afx_device.h) with ONE round of workgroups -- the waves
+// of a workgroup claim their runs, so a second round only adds a second set of tails (profiles/r07_ab_headline.txt); a call that
+// cannot fill the round with 16-frame runs is spread over all CUs as before.  AFX_MEL_CUS=N sizes the grid as if the device had N CUs
+// (the tests' way to long ranges per workgroup on few frames; read per launch)
+long long wg_ranges(long long total, int waves, long long *framesPerWg) {
+    const char *e = getenv("AFX_MEL_CUS");
+    const int asked = e ? atoi(e) : 0;
+    const int cus = asked > 0 ? asked : afx_cu_count();
+    long long fpw;
+    long long blocks = afx_frame_split(total, cus, waves, 1, &fpw);
+    *framesPerWg = fpw * waves;
+    if (*framesPerWg > (1ll << 30)) {  // the claim counter is one 32-bit word
+        *framesPerWg = 1ll << 30;
+        blocks = (total + *framesPerWg - 1) / *framesPerWg;
+    }
+    return blocks;
+}
+
+#ifdef AFX_V2_STAMPS
+// diagnostic builds: a fresh stamp buffer per launch; after the launch it is waited for and written to AFX_V2_STAMPS_FILE
+unsigned long long *stamps_begin(long long blocks, int waves) {
+    unsigned long long *d = nullptr;
+    const size_t n = (size_t)blocks * waves * STAMP_WORDS * 8;
+    if (hipMalloc(&d, n) != hipSuccess || hipMemset(d, 0, n) != hipSuccess) return nullptr;
+    return d;
+}
+void stamps_end(unsigned long long *d, long long blocks, int waves, void *stream) {
+    const size_t n = (size_t)blocks * waves * STAMP_WORDS;
+    std::vector<unsigned long long> h(n);
+    (void)hipStreamSynchronize((hipStream_t)stream);
+    if (hipMemcpy(h.data(), d, n * 8, hipMemcpyDeviceToHost) == hipSuccess)
+        if (const char *name = getenv("AFX_V2_STAMPS_FILE"))
+            if (FILE *fp = fopen(name, "wb")) {
+                fwrite(h.data(), 8, n, fp);
+                fclose(fp);
+            }
+    (void)hipFree(d);
+}
+#endif
+
 template <int TA, int TB, int SHIFT, bool SPLIT, int CC, bool TEMPORAL, bool CPLX = false>
 int launch_variant(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
     const long long total = (long long)a->batch * a->timeLength;
     if (total <= 0) return AFX_OK;
     constexpr int NWV = waves_of(CPLX);
-    long long fpw;
-    const long long blocks = afx_mel_frames(total, NWV, &fpw);
+    long long fpg;
+    const long long blocks = wg_ranges(total, NWV, &fpg);
 
     KArgs2 k;
     memset(&k, 0, sizeof(k));
@@ -652,7 +778,7 @@ int launch_variant(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) 
     k.totalFrames = total;
     k.timeLength = a->timeLength;
     k.hop = a->hop;
-    k.framesPerWave = (int)fpw;
+    k.framesPerWg = fpg;
     k.aligned = ((a->clipStride & 1) == 0) && ((a->hop & 1) == 0) && ((reinterpret_cast<uintptr_t>(a->x) & 7) == 0);
     k.tab = reinterpret_cast<const float4 *>(p->dTab);
     k.meta = p->dMeta;
@@ -671,8 +797,14 @@ int launch_variant(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) 
     k.zcr = a->zcr;
     constexpr size_t lds = (size_t)block_lds_bytes(TA, TB, CC == 1);
     static_assert(lds <= 163840, "workgroup LDS budget");
+#ifdef AFX_V2_STAMPS
+    if (!(k.stamps = stamps_begin(blocks, NWV))) return AFX_ERR_HIP;
+#endif
     AFX_LAUNCH_DYN_LDS((k_stft_mel_v2<TA, TB, SHIFT, SPLIT, CC, TEMPORAL, CPLX>), dim3((unsigned)blocks), dim3(NWV * 64), lds, stream, k);
     AFX_LAUNCH_CHECK("k_stft_mel_v2");
+#ifdef AFX_V2_STAMPS
+    stamps_end(k.stamps, blocks, NWV, stream);
+#endif
     return AFX_OK;
 }
 
@@ -732,8 +864,8 @@ void fill_stft_tables(float *tab) { fill_tables(tab, nullptr); }  // the twiddle
 template <int SHIFT>
 int launch_stft2k(const AfxStftArgs *a, const float *tab, void *stream) {
     const long long total = (long long)a->batch * a->timeLength;
-    long long fpw;
-    const long long blocks = afx_mel_frames(total, WAVES, &fpw);
+    long long fpg;
+    const long long blocks = wg_ranges(total, WAVES, &fpg);
     KArgs2 k;
     memset(&k, 0, sizeof(k));
     k.x = a->x;
@@ -741,7 +873,7 @@ int launch_stft2k(const AfxStftArgs *a, const float *tab, void *stream) {
     k.totalFrames = total;
     k.timeLength = a->timeLength;
     k.hop = a->hop;
-    k.framesPerWave = (int)fpw;
+    k.framesPerWg = fpg;
     k.aligned = ((a->clipStride & 1) == 0) && ((a->hop & 1) == 0) && ((reinterpret_cast<uintptr_t>(a->x) & 7) == 0);
     k.tab = reinterpret_cast<const float4 *>(tab);
     k.specMap = a->mode == AFX_SPEC_POWER ? 0 : a->mode == AFX_SPEC_MAG ? 1 : 2;
@@ -754,8 +886,14 @@ int launch_stft2k(const AfxStftArgs *a, const float *tab, void *stream) {
     k.vecOut = a->binLo == 0 && a->binCount == NFFT / 2 + 1 && k.outPitch >= 1028 && (k.outPitch & 3) == 0 &&
                (reinterpret_cast<uintptr_t>(a->outRe) & 15) == 0;
     constexpr size_t lds = (size_t)block_lds_bytes(0, 0, false);
+#ifdef AFX_V2_STAMPS
+    if (!(k.stamps = stamps_begin(blocks, WAVES))) return AFX_ERR_HIP;
+#endif
     AFX_LAUNCH_DYN_LDS((k_stft_mel_v2<0, 0, SHIFT, false, 0, false, false, true>), dim3((unsigned)blocks), dim3(WAVES * 64), lds, stream, k);
     AFX_LAUNCH_CHECK("k_stft_mel_v2 (stft)");
+#ifdef AFX_V2_STAMPS
+    stamps_end(k.stamps, blocks, WAVES, stream);
+#endif
     return AFX_OK;
 }
 
