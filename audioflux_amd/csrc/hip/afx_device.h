@@ -179,8 +179,11 @@ int afxk_gemm_nt(const float *A, long long lda, const float *B, int ldb,
                  float *C, long long ldc, long long M, int N, int K,
                  int pre, int post, float postArg, void *stream);
 
-/* the same product with every operand as three bf16 words on the bf16 matrix cores (afx_gemm_bf16.hip;
- * AFX_GEMM_BF16=1, off by default); pre is AFX_MAP_NONE; AFX_ERR_UNSUPPORTED for unaligned operands */
+/* the same product with every operand as three bf16 words on the bf16 matrix cores (afx_gemm_bf16.hip,
+ * k_gemm_nt128_bf16x3): what afxk_gemm_nt runs for every product with N > 32 and no pre-map whose operands it takes;
+ * pre is AFX_MAP_NONE; AFX_ERR_UNSUPPORTED for A or B off a 16-byte boundary or a pitch that is no multiple of 4 floats
+ * (afxk_gemm_nt then runs the float32 kernel).  Non-finite values of A and B give the IEEE product (the split puts them
+ * whole into the low word, which meets only the other operand's high word). */
 int afxk_gemm_nt128_bf16(const float *A, long long lda, const float *B, int ldb, float *C, long long ldc,
                          long long M, int N, int K, int post, float postArg, void *stream);
 
@@ -188,7 +191,9 @@ int afxk_gemm_nt128_bf16(const float *A, long long lda, const float *B, int ldb,
  * afxk_gemm_bank_prepare splits bank[N, K] (device, row pitch ldb floats) into its three bf16 word planes in the order the
  * kernel stages them ("bank image", device memory owned by the caller: afxdev_free); afxk_gemm_nt_bank computes
  * C[M, N] = post(A[M, K] . bank^T) with the float32 rows of A split while they are staged.  A: 16-byte aligned, lda a
- * multiple of 4 floats; AFX_ERR_UNSUPPORTED otherwise (callers then run afxk_gemm_nt on the float bank).
+ * multiple of 4 floats and at least K rounded up to 4 (the last quad of a row is read whole; what it holds behind K, NaN
+ * included, reaches no result); AFX_ERR_UNSUPPORTED otherwise (callers then run afxk_gemm_nt on the float bank).
+ * Every float32 value of A and of the bank is taken: +-Inf, NaN and values next to FLT_MAX give the IEEE product.
  * The reference's product: __mdot1, src/vector/flux_vector.c:55-86 */
 int afxk_gemm_bank_prepare(const float *B, int ldb, int N, int K, void **bankImage, void *stream);
 int afxk_gemm_nt_bank(const float *A, long long lda, const void *bankImage, int N, int K, float *C, long long ldc,

@@ -51,16 +51,23 @@ constexpr int OPER = 3 * PLANE;               // hi | mid | lo
 constexpr int STAGE = 2 * OPER;               // A | B
 constexpr int LDS_BYTES = 2 * STAGE;          // double buffer: 73 728 bytes
 
-// four float32 -> the three bf16 words of each (round to nearest even; remainders exact)
+// four float32 -> the three bf16 words of each (round to nearest even; remainders exact).  The split is total: a finite
+// value that the conversion would round up to the Inf pattern (|x| >= 0x7f7f8000) takes the truncated hi word and stays exact;
+// +-Inf and NaN go WHOLE into the lo word, hi and mid are zero.  The lo word of one operand meets only the hi word of the
+// other (the six terms below), and that word has the sign of its value and is zero only when the value is: Inf . b comes out
+// as the IEEE product, where an Inf hi word would meet mid / lo words of either sign (Inf - Inf) or zero (Inf . 0).
 __device__ __forceinline__ void split3(const f32x4 v, bf4 &h, bf4 &m, bf4 &l) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        const __bf16 hh = (__bf16)v[c];
-        const float r1 = v[c] - (float)hh;
-        const __bf16 mm = (__bf16)r1;
-        const float r2 = r1 - (float)mm;
-        h[c] = hh;
-        m[c] = mm;
+        const float x = v[c], ax = fabsf(x);
+        const bool fin = ax < __builtin_inff();
+        float hf = (float)(__bf16)x;
+        if (!(ax < __uint_as_float(0x7f7f8000u))) hf = fin ? __uint_as_float(__float_as_uint(x) & 0xffff0000u) : 0.f;
+        const float r1 = x - hf;
+        const float mf = fin ? (float)(__bf16)r1 : 0.f;
+        const float r2 = r1 - mf;
+        h[c] = (__bf16)hf;
+        m[c] = (__bf16)mf;
         l[c] = (__bf16)r2;
     }
 }
@@ -229,19 +236,43 @@ __device__ __forceinline__ float u2f(unsigned x) { return __uint_as_float(x); }
 // upper half-words of (x0, x1) as (low, high) half of one word
 __device__ __forceinline__ unsigned pack_hi(unsigned x0, unsigned x1) { return (x1 & 0xffff0000u) | (x0 >> 16); }
 
-// One float32 -> its three bf16 words, in two halves (the pieces the kernel places between its MFMAs).  hi and mid are ROUNDED
-// (half up in magnitude: one integer add before the mask), lo takes what is left: |r1| <= 2^-9 |x| has at most 16 significant
-// bits, |r2| <= 2^-9 |r1| at most 7 -- the split is exact.  (Plain truncation is exact as well and two instructions shorter,
+// One float32 -> its three bf16 words, in two halves of five vector instructions (the pieces the kernel places between its MFMAs).
+// hi and mid are ROUNDED (half up in magnitude: one integer add before the mask), lo takes what is left: |r1| <= 2^-9 |x| has at
+// most 16 significant bits, |r2| <= 2^-9 |r1| at most 7 -- the split is exact.  (Plain truncation is exact as well and shorter,
 // but leaves every word with the sign of x: the small terms of the product, all of one sign, are then rounded away one by one
 // against the large accumulator -- a bias of -2.4e-6 of the result at K = 1025 under tests/emu, against 5e-7 for words of
-// either sign.)
-__device__ __forceinline__ void split_hi(float x, unsigned &hb, float &r1) {
-    hb = (f2u(x) + 0x8000u) & 0xffff0000u;
-    r1 = x - u2f(hb);
+// either sign.)  The split is TOTAL: a finite value whose rounded hi word would be the Inf pattern (|x| >= 0x7f7f8000) is not
+// rounded up -- its hi word is the truncated one, the remainders stay exact; +-Inf and NaN keep no hi and no mid word (`keep`
+// = 0) and arrive whole in the lo word, r2 = x - 0 - 0.  The lo word of one operand meets only the hi word of the other, which
+// has the sign of its value and is zero only where the value is: Inf . b is the IEEE product (+-Inf, NaN for b = 0), where an
+// Inf hi word would meet mid and lo words of either sign or zero (Inf - Inf, Inf . 0: NaN in every column).
+// first half: the rounded bits and the mask of the hi / mid words
+__device__ __forceinline__ void split_hi(float x, unsigned &s, unsigned &keep) {
+    const float ax = fabsf(x);
+    s = f2u(x) + (ax < u2f(0x7f7f8000u) ? 0x8000u : 0u);
+    keep = ax < __builtin_inff() ? 0xffff0000u : 0u;
 }
-__device__ __forceinline__ void split_mid(float r1, unsigned &mb, float &r2) {
-    mb = (f2u(r1) + 0x8000u) & 0xffff0000u;
+// second half: hi word, mid word, what is left
+__device__ __forceinline__ void split_mid(float x, unsigned s, unsigned keep, unsigned &hb, unsigned &mb, float &r2) {
+    hb = s & keep;
+    const float r1 = x - u2f(hb);
+    mb = (f2u(r1) + 0x8000u) & keep;
     r2 = r1 - u2f(mb);
+}
+// upper half-words of (w0, w1) as (low, high) half of one word; a selector half of 0x0c0c instead of 0x0302 / 0x0706 gives zero
+constexpr unsigned PACK_UPPER = 0x07060302u;
+__device__ __forceinline__ unsigned pack_sel(unsigned w0, unsigned w1, unsigned sel) {
+#if __has_builtin(__builtin_amdgcn_perm)
+    return __builtin_amdgcn_perm(w1, w0, sel);  // v_perm_b32: selector bytes 0-3 take from w0, 4-7 from w1, 0x0c gives 0x00
+#else  // (the host build of tests/emu: the same byte selection in plain C++)
+    const unsigned long long v = ((unsigned long long)w1 << 32) | w0;
+    unsigned d = 0;
+    for (int i = 0; i < 4; ++i) {
+        const unsigned c = (sel >> (8 * i)) & 0xffu;
+        if (c < 8) d |= ((unsigned)(v >> (8 * c)) & 0xffu) << (8 * i);
+    }
+    return d;
+#endif
 }
 
 // bank [N, K] (row pitch ldb floats) -> image; one thread per 8 words of a row: row r = 64 wc + 32 tj + i of the tile, k-block g
@@ -257,9 +288,9 @@ __global__ __launch_bounds__(256) void k_bank_split(const float *__restrict__ B,
     for (int c = 0; c < 8; ++c) {
         const int k = k0 + c;
         const float x = (n < N && k < K) ? B[(long long)n * ldb + k] : 0.f;
-        float r1;
-        split_hi(x, hb[c], r1);
-        split_mid(r1, mb[c], r2[c]);
+        unsigned s, keep;
+        split_hi(x, s, keep);
+        split_mid(x, s, keep, hb[c], mb[c], r2[c]);
     }
     u32x4 *dst = img + (size_t)blockIdx.x * IMG_U4 + (size_t)(row >> 5) * 3 * 64 + (row & 31) + 32 * g;
     dst[0] = u32x4{hb[1] | (hb[0] >> 16), hb[3] | (hb[2] >> 16), hb[5] | (hb[4] >> 16), hb[7] | (hb[6] >> 16)};
@@ -344,32 +375,33 @@ __global__ __launch_bounds__(256) AFX_WAVES_PER_EU(2, 2) void k_gemm_bank_bf16x3
     // this thread's words in a stage of the LDS: k-step half ph, rows lr + 32 j, 8 bytes per plane
     const int aoff = ph * OPER + lr * ROW + 8 * kq;
     // words at k >= K are padding in A (zeros in the image): NaNs there must not reach a product.  Only the last stage has
-    // such words; the select is written without a branch so that the split stays in the block of the MFMAs
-    bool tm[4];
+    // such words.  They go through the split like any other (nothing traps) and are dropped where the half-words are packed:
+    // the byte selector of the last stage takes zeros in their place -- no select in the split, no branch in the block of the MFMAs
+    unsigned selTail[2];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) tm[c] = 32 * (ns - 1) + 4 * pq + c >= K;
+    for (int p = 0; p < 2; ++p) {
+        const bool t0 = 32 * (ns - 1) + 4 * pq + 2 * p >= K, t1 = 32 * (ns - 1) + 4 * pq + 2 * p + 1 >= K;
+        selTail[p] = (t1 ? 0x0c0c0000u : PACK_UPPER & 0xffff0000u) | (t0 ? 0x0c0cu : PACK_UPPER & 0xffffu);
+    }
 
-    // the split of one quad, as numbered pieces (0-7: hi / mid halves of its four values, 8-9: packs + stores); state between them
-    unsigned hb[4], mbw[4];
-    float r1[4], r2[4];
-    auto piece = [&](int jj, const f32x4 &q, bool last, unsigned char *dst) {
+    // the split of one quad, as numbered pieces (0-7: the two halves of its four values, 8-9: packs + stores); state between them
+    unsigned sb[4], keep[4], hb[4], mbw[4];
+    float r2[4];
+    auto piece = [&](int jj, const f32x4 &q, const unsigned *sel, unsigned char *dst) {
         if ((AFX_KO_GEMM & 16) && jj < 8) return;
         if ((AFX_KO_GEMM & 8) && jj >= 8) return;
         if (jj < 8) {
             const int c = jj >> 1;
-            if ((jj & 1) == 0) {
-                const float x = (last && tm[c]) ? 0.f : q[c];
-                split_hi(x, hb[c], r1[c]);
-            } else {
-                split_mid(r1[c], mbw[c], r2[c]);
-            }
+            if ((jj & 1) == 0) split_hi(q[c], sb[c], keep[c]);
+            else split_mid(q[c], sb[c], keep[c], hb[c], mbw[c], r2[c]);
         } else if (jj == 8) {
-            *reinterpret_cast<u32x2 *>(dst) = u32x2{hb[1] | (hb[0] >> 16), hb[3] | (hb[2] >> 16)};
-            *reinterpret_cast<u32x2 *>(dst + PLANE) = u32x2{mbw[1] | (mbw[0] >> 16), mbw[3] | (mbw[2] >> 16)};
+            *reinterpret_cast<u32x2 *>(dst) = u32x2{pack_sel(hb[0], hb[1], sel[0]), pack_sel(hb[2], hb[3], sel[1])};
+            *reinterpret_cast<u32x2 *>(dst + PLANE) = u32x2{pack_sel(mbw[0], mbw[1], sel[0]), pack_sel(mbw[2], mbw[3], sel[1])};
         } else {
-            *reinterpret_cast<u32x2 *>(dst + 2 * PLANE) = u32x2{pack_hi(f2u(r2[0]), f2u(r2[1])), pack_hi(f2u(r2[2]), f2u(r2[3]))};
+            *reinterpret_cast<u32x2 *>(dst + 2 * PLANE) = u32x2{pack_sel(f2u(r2[0]), f2u(r2[1]), sel[0]), pack_sel(f2u(r2[2]), f2u(r2[3]), sel[1])};
         }
     };
+    const unsigned selAll[2] = {PACK_UPPER, PACK_UPPER};
 
     // prologue: fragments of k-step 0, A quads of stages 0 and 1; stage 0 split into the first buffer
     gload_b(0, rb[0]);
@@ -380,7 +412,7 @@ __global__ __launch_bounds__(256) AFX_WAVES_PER_EU(2, 2) void k_gemm_bank_bf16x3
     for (int j = 0; j < 4; ++j) {
         PIN(ra[0][j]);
 #pragma unroll
-        for (int jj = 0; jj < 10; ++jj) piece(jj, ra[0][j], ns == 1, smem + aoff + 32 * j * ROW);
+        for (int jj = 0; jj < 10; ++jj) piece(jj, ra[0][j], ns == 1 ? selTail : selAll, smem + aoff + 32 * j * ROW);
     }
     __syncthreads();
     const int fragOff = (lane & 31) * ROW + 16 * (lane >> 5);
@@ -391,6 +423,7 @@ __global__ __launch_bounds__(256) AFX_WAVES_PER_EU(2, 2) void k_gemm_bank_bf16x3
             if (st >= ns) break;
             f32x4(&an)[4] = ra[u ^ 1];  // stage st + 1: split into the other buffer while this one is multiplied
             const bool last = st + 1 == ns - 1;
+            const unsigned sel[2] = {last ? selTail[0] : PACK_UPPER, last ? selTail[1] : PACK_UPPER};
             unsigned char *nbase = smem + (u ^ 1) * STAGE + aoff;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -426,7 +459,7 @@ __global__ __launch_bounds__(256) AFX_WAVES_PER_EU(2, 2) void k_gemm_bank_bf16x3
                     else acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ti][wa], rb[h][tj][wb], acc[ti][tj], 0, 0, 0);
                     if (m < 20) {  // quads 2 h and 2 h + 1 of the next stage: ten pieces each
                         const int j = 2 * h + (m >= 10);
-                        piece(m >= 10 ? m - 10 : m, an[j], last, nbase + 32 * j * ROW);
+                        piece(m >= 10 ? m - 10 : m, an[j], sel, nbase + 32 * j * ROW);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }

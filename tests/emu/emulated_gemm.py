@@ -2,12 +2,19 @@
 """k_gemm_nt128_bf16x3 (audioflux_amd/csrc/hip/afx_gemm_bf16.hip: written without hardware access) on the CPU: its
 device code compiled for the host (tests/emu) computes C = A B^T for power-spectrum-like operands spanning ten decades
 per row, odd sizes (row / column / k tails, pitched operands), with and without the power-law epilogue, and is compared
-ELEMENTWISE with a float64 product.  AFX_LIB = the library tests/test_emulated_kernels.py builds."""
+ELEMENTWISE with a float64 product.  Then the table of tests/gemm_cases.py -- every case of the two bf16 entry points, the cases
+and bars of the device test tests/test_gemm_gpu.py -- through the same runner (tests/gemm_check.py) on host memory, the documented
+refusals, and the non-finite operands of the device test.  (k_gemm_nt is not part of this library: its launcher is the stand-in's.)
+AFX_LIB = the library tests/test_emulated_kernels.py builds."""
 import ctypes as C
 import os
 import sys
 
 import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from tests import gemm_cases as gc  # noqa: E402
+from tests import gemm_check as chk  # noqa: E402
 
 lib = C.CDLL(os.environ["AFX_LIB"])
 fp = C.POINTER(C.c_float)
@@ -95,7 +102,40 @@ def main():
     run_bank(130, 40, 1025, 1028, 1028, 40, AFX_MAP_POW, 0.5, 3)  # the dense filter-bank shape, 65 k-steps, one word in the last
     run_bank(70, 128, 33, 36, 36, 128, 0, 0.0, 4, signed=True)    # three k-steps (fewer than the ring), signed rows
     run_bank(5, 12, 7, 8, 8, 12, 0, 0.0, 5)            # one k-step
+    table(AFX_MAP_POW)
     print("OK")
+
+
+def table(map_pow):
+    """the device test's table on the emulated kernels; a case over its bar here is a finding about this emulation's MFMA
+    accumulate (tests/emu/hip/hip_runtime.h adds the sixteen products of a k-step one by one), never a reason for another bar"""
+    assert map_pow == gc.MAP_POW
+    n, over = 0, []
+    for case in gc.table():
+        if case.kernel != "f32":
+            try:
+                chk.run_case(lib, "numpy", None, None, case)
+            except AssertionError as e:  # (every case runs: the list of those over their bars is the finding)
+                over.append(str(e))
+            n += 1
+    chk.check_refusals(lib, "numpy", None, None)
+    print(f"table: {n} cases, {len(over)} over their bars", flush=True)
+    assert not over, "\n".join(over)
+    r = chk.Runner(lib, "numpy", None, None)
+    for K in (17, 77):  # Inf, FLT_MAX and NaN in A: the rows they are in, and no other
+        special, plain, B, _ = gc.special_operands(K)
+        up = (K + 3) & ~3
+        for kernel in ("bank", "nt128"):
+            got, ref = (chk.split_result(r.product(kernel, A, B, up + 4, up + 8, 133)[1], 130)[0] for A in (special, plain))
+            others = np.setdiff1d(np.arange(130), list(gc.SPECIAL_ROWS))
+            assert np.array_equal(got[others].view(np.uint32), ref[others].view(np.uint32)), (kernel, K)
+            assert np.isposinf(got[3]).all() and np.isnan(got[129]).all(), (kernel, K, got[3][:8], got[129][:8])
+            want = special[70].astype(np.float64) @ B.astype(np.float64).T
+            judged, over = gc.row70_mask(want), want > gc.FLT_MAX
+            assert np.isposinf(got[70][judged & over]).all() and np.isfinite(got[70][judged & ~over]).all(), (kernel, K)
+            rel = np.abs(got[70][judged & ~over] - want[judged & ~over]) / want[judged & ~over]
+            assert rel.max() <= 1e-6, (kernel, K, rel.max())
+            print(f"non-finite operands, {kernel}, K {K}: row 70 within {rel.max():.1e}")
 
 
 if __name__ == "__main__":

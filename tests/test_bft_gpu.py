@@ -457,7 +457,8 @@ def test_temporal_features_beside_the_other_fused_kernels(r2, rt):
 @pytest.mark.parametrize("rt,dt", [(1, 0), (1, 1), (0, 0)])
 def test_dense_bank_at_the_headline_shape(rt, dt):
     """Dense (gammatone) bank at n_fft 2048 / 128 bands: STFT wave kernel -> pitched [T,F] scratch ->
-    128 x 128 MFMA GEMM (k_gemm_nt128), chunked; real power / magnitude and complex results against the
+    the prepared-bank product (k_bank_split once per object, k_gemm_bank_bf16x3 per chunk: 128 x 128 tiles, three bf16
+    words per operand; element by element in tests/test_gemm_gpu.py), chunked; real power / magnitude and complex results against the
     reference's double-accumulating __mdot1 (flux_vector.c:55-86) on several clips (more than one chunk
     with AFX_SCRATCH_MB=1)."""
     xs = np.stack([cases.noise(80 + i, 16000 * 2 + 50) for i in range(3)])

@@ -209,10 +209,16 @@ def test_time_domain_cwt_kernel_emulated(emulated):
 
 
 def test_bf16x3_gemm_emulated_matches_float64(emulated):
-    """k_gemm_nt128_bf16x3: loader / three-word split / 24 MFMAs per k-step / epilogue with every
-    tail, elementwise against float64 on operands spanning ten decades"""
+    """k_gemm_nt128_bf16x3 and k_bank_split + k_gemm_bank_bf16x3: loader / three-word split / 24 MFMAs per k-step / epilogue with
+    every tail, elementwise against float64 on operands spanning ten decades; then the whole table of tests/test_gemm_gpu.py for
+    these two entry points through the same runner, its refusals and its non-finite operands"""
     out = _run(emulated, "emulated_gemm.py", [])
     assert out.count("elementwise relative error") == 8 and out.count("bank form") == 5
+    # the table of the device test (tests/gemm_cases.py) on the two bf16 entry points, every case at the device test's bar
+    from tests import gemm_cases
+    n = sum(c.kernel != "f32" for c in gemm_cases.table())
+    assert n >= 100 and out.count("elementwise error max") == n and f"table: {n} cases, 0 over their bars" in out, out[-2000:]
+    assert out.count("non-finite operands") == 4
 
 
 def test_dense_route_producer_emulated_against_float64(emulated):
