@@ -471,6 +471,12 @@ int afx_cwt_create_custom(CWTObj *cwtObj, int num, int radix2Exp, int samplate, 
                           const float *bank, const float *fre, const int *bin, const char *who) {
     long long fftLength;
     int rL;
+    if (cwtObj) *cwtObj = NULL;
+    if (!cwtObj || !bank || !fre || !bin || num < 1 || radix2Exp < 1 || radix2Exp > 30) {
+        /* (a NULL bank would fall through to the analytic bank of an all-zero parameter set) */
+        afxdev_set_error("%s: bad argument", who ? who : "afx_cwt_create_custom");
+        return AFX_ERR_ARG;
+    }
     const int pad = pad_rule(radix2Exp, isPadding, who, &fftLength, &rL);
     if (pad < 0) return pad;
     struct OpaqueCWT proto;
@@ -927,6 +933,17 @@ void afx_cwt_classify_host(const int *sup, int num, int maxR, int *order, int *n
     }
 }
 
+int afx_cwt_plan_counts(CWTObj o, int out[10]) {
+    if (!o || !out) return AFX_ERR_ARG;
+    memset(out, 0, sizeof(int) * 10);
+    if (!o->dims.order) return AFX_OK; /* no order list: every scale takes the size's one path */
+    out[0] = o->dims.nTd;
+    out[1] = o->dims.tdDet != NULL;
+    out[2] = o->dims.nWide;
+    for (int c = 0; c < 7; c++) out[3 + c] = o->dims.nNarrow[c];
+    return AFX_OK;
+}
+
 float *cwtObj_getFreBandArr(CWTObj o) { return o ? o->freBandArr : NULL; }
 int *cwtObj_getBinBandArr(CWTObj o) { return o ? o->binBandArr : NULL; }
 
@@ -1028,7 +1045,9 @@ static int cwt_batch_device(CWTObj o, const float *dData, int chunks, long long 
         if (st == AFX_OK)
             st = afxk_cwt_td(tdPlan, dData, chunkStride, chunks, o->dataLength, o->num, dReal, dImag, tds, NULL);
     }
-    const int nTwoPass = o->dims.order ? o->dims.nWide + (useTd ? 0 : o->dims.nTd) : o->num; /* scales that write the intermediate */
+    /* scales that write the intermediate (AFX_NO_FUSED: the size-generic inverse takes every scale through it, whatever
+     * the order list says -- a bank of narrow-band scales only would otherwise leave it unreserved) */
+    const int nTwoPass = o->dims.order && !afxdev_no_fused() ? o->dims.nWide + (useTd ? 0 : o->dims.nTd) : o->num;
     /* (no two-pass scale at all: the group only paces the loop below -- one forward batch) */
     /* (two chains of 48 MB each: round 2's three-stream schedule, +10 % over one stream) */
     int group = nTwoPass > 0 ? (int)(48.0e6 / ((double)nTwoPass * L * 8.0)) : 32;

@@ -89,6 +89,11 @@ long long afx_cwt_fft_length(int radix2Exp, int isPadding);
  * the execution order wide scales | classes R = 2, 4, 8, 16 | two-block classes R = 20, 24, 32 (see afx_device.h) */
 void afx_cwt_support_host(const float *bank, int num, long long fftLength, int r1, int *sup);
 void afx_cwt_classify_host(const int *sup, int num, int maxR, int *order, int *nWide, int nNarrow[7]);
+/* the plan an object ended up with (read-only, for tests): out[0] scales in the time-domain kernel, out[1] 1 when the
+ * derivative bank has time-domain images of its own (after cwtObj_enableDet), out[2] two-pass scales, out[3..9] the
+ * narrow-band classes R = 2, 4, 8, 16, 20, 24, 32.  All zero where the object has no order list: every transform length
+ * but 2^17, and AFX_CWT_NARROW_MAX below 2 (every scale then takes both passes). */
+int afx_cwt_plan_counts(struct OpaqueCWT *o, int out[10]);
 /* widest narrow-band class used unless AFX_CWT_NARROW_MAX says otherwise (0: every scale takes
  * both passes).  BASELINE cfg 4, round 3 (profiles/r03_cwt_nb2.txt): 20 -- the four scales of 17 ... 20 rows that
  * are too long for the time-domain kernel -- 34.5 k chunks/s; 16: 33.2 k; 24 / 32 take scales away from the
