@@ -13,6 +13,7 @@ from .cepstrogram import Cepstrogram
 from .cqt import CQT
 from .cwt import CWT
 from .pwt import PWT
+from .nsgt import NSGT
 from .reassign import Reassign
 from .stft import STFT
 from .hpss import HPSS, median_filter_device
@@ -23,6 +24,6 @@ from .spectrogram import (Bark, BarkSpectrogram, Chroma, Erb, ErbSpectrogram, Li
                           Spectrogram, SpectrogramBase, SpectralFilterBankType)
 from .batch import mel_mfcc_device
 
-__all__ = ["BFT", "XXCC", "Spectral", "SpectralNoveltyMethodType", "SpectralNoveltyDataType", "Cepstrogram", "CQT", "CWT", "PWT", "Reassign", "STFT", "HPSS", "median_filter_device", "PitchYIN", "Synsq", "WSST", "Spectrogram", "SpectrogramBase", "MelSpectrogram", "BarkSpectrogram", "ErbSpectrogram",
+__all__ = ["BFT", "XXCC", "Spectral", "SpectralNoveltyMethodType", "SpectralNoveltyDataType", "Cepstrogram", "CQT", "CWT", "PWT", "NSGT", "Reassign", "STFT", "HPSS", "median_filter_device", "PitchYIN", "Synsq", "WSST", "Spectrogram", "SpectrogramBase", "MelSpectrogram", "BarkSpectrogram", "ErbSpectrogram",
            "Linear", "Mel", "Bark", "Erb", "Chroma", "SpectralFilterBankType", "mel_mfcc_device", "get_lib", "build", "runtime_status",
            "last_error", "LIB_PATH"]

@@ -1002,6 +1002,14 @@ extern "C" int afxk_cwt_forward(const AfxCwtPlanDims *d, const float *tw, const 
     return AFX_OK;
 }
 
+// The NSGT's spectrum (afx_nsgt.hip reads it): this forward pass without padding, under a name of its own.  The result
+// is the full complex spectrum in the TRANSPOSED layout Xt[k1][k2], frequency k1 + 2^r1 k2.
+extern "C" int afxk_nsgt_spectrum(const AfxCwtPlanDims *d, const float *tw, const float *x, long long xStride,
+                                  int chunks, float *scratchA, float *Xt, void *stream) {
+    if (!d || !tw || !x || !scratchA || !Xt || d->pad != 0 || d->dataLength != 1 << (d->r1 + d->r2)) return AFX_ERR_ARG;
+    return afxk_cwt_forward(d, tw, x, xStride, chunks, scratchA, Xt, stream);
+}
+
 extern "C" int afxk_cwt_inverse(const AfxCwtPlanDims *d, const float *tw, const float *Xt,
                                 const float *bankT, int num, int isDet, int chunks, float *scratchB,
                                 float *outRe, float *outIm, int parts, void *stream) {

@@ -597,6 +597,43 @@ typedef struct {
  * AFX_ERR_ARG for a plan outside the limits above, AFX_ERR_UNSUPPORTED beyond 2^31 - 1 frames in a launch. */
 int afxk_pitch_yin(const AfxPitchYinArgs *a, void *stream);
 
+/* ---- non-stationary Gabor transform (afx_nsgt.hip) ------------------------- */
+#define AFX_NSGT_TILE 512  /* spectrum values (and twiddles) of a band one wave keeps in LDS; longer bands tile k */
+#define AFX_NSGT_BLOCK 256 /* outputs n of one work item: 4 accumulators per lane */
+typedef struct {
+    int len;      /* L: window length = length of the band's inverse DFT = its cells                  */
+    int offset;   /* first spectrum bin under the window (reads are clamped to 0 ... N - 1)           */
+    int cell;     /* start of the band's cells in [totalLength]; its windows start there too          */
+    int twiddle;  /* start (in float2) of the length's table T_L[m] = (cos, sin)(2 pi m / L), m < L   */
+    int cellCol;  /* start of the band's L + 1 entries in cellCol: entry n = first matrix column whose
+                   * cell index is >= n (entry L = maxLength)                                          */
+} AfxNsgtBand;
+typedef struct {
+    int r1, r2;              /* N = 2^(r1 + r2); frequency k of chunk c at Xt[c][k & (2^r1 - 1)][k >> r1]  */
+    int num, maxLength, totalLength;
+    const AfxNsgtBand *bands;   /* device [num]                                                            */
+    const int *items;        /* device [nItems][2]: (band, first output n of the block), long bands first  */
+    int nItems;
+    const float *window;     /* device [totalLength]                                                       */
+    const float *twiddle;    /* device float2 tables, one per distinct length                              */
+    const int *colMap;       /* device [num][maxLength]: cell index (0 ... L - 1) each matrix column holds  */
+    const int *cellCol;      /* device: see AfxNsgtBand                                                    */
+    const float *Xt;         /* device [chunks][N] complex: afxk_nsgt_spectrum's result                    */
+    int chunks;              /* <= 65535 per launch                                                        */
+    float *outRe, *outIm;    /* device [chunks][num][maxLength]: every element is written                   */
+    float *cellRe, *cellIm;  /* device [chunks][totalLength], or both NULL: not stored                      */
+} AfxNsgtArgs;
+/* `chunks` real signals of N = 2^(r1 + r2) samples, chunk c at x + c xStride -> their full complex spectra
+ * Xt[c][k1][k2] (TRANSPOSED layout: frequency k1 + 2^r1 k2 at [k1][k2]); scratchA: chunks * N complex.  The forward pass
+ * of the CWT (afxk_cwt_forward, pad 0) under a name of its own.  d: r1, r2, dataLength = N, pad 0, tileCols. */
+int afxk_nsgt_spectrum(const AfxCwtPlanDims *d, const float *tw, const float *x, long long xStride, int chunks,
+                       float *scratchA, float *Xt, void *stream);
+/* per band and chunk: window multiply on the spectrum slice, rotation by L - L / 2, inverse DFT of the band's own length
+ * L (any L >= 1), 1 / L, cell store, and the sample-and-hold gather into the matrix row -- one launch, one wave per
+ * (band, chunk, block of AFX_NSGT_BLOCK outputs).  AFX_ERR_ARG for a NULL plan / output, AFX_ERR_UNSUPPORTED beyond the
+ * launch limits (chunks > 65535). */
+int afxk_nsgt_bands(const AfxNsgtArgs *a, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

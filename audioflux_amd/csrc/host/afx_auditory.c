@@ -63,6 +63,8 @@ float afx_log_to_fre(float value, float binPerOctave) {
     return (float)(pow(2, value / binPerOctave) * 440);
 }
 
+static float fre_to_linear(float f, float det) { return roundf(f / det); }
+static float linear_to_fre(float v, float det) { return v * det; }
 static float fre_to_logspace(float f, float ref) { (void)ref; return (float)log2(f / 440); }
 static float logspace_to_fre(float v, float ref) { (void)ref; return (float)(pow(2, v) * 440); }
 
@@ -327,13 +329,9 @@ static int style_gammatone(int num, int fftLength, int samplate,
     return AFX_OK;
 }
 
-int afx_auditory_bank(int num, int fftLength, int samplate, SpectralFilterBankScaleType scale,
-                       SpectralFilterBankStyleType style, SpectralFilterBankNormalType normal,
-                       float lowFre, float highFre, int binPerOctave, float *bank, float *freOut,
-                       int *binOut) {
-    const int isEdge = (style == SpectralFilterBankStyle_Gammatone);
-    const int offset = isEdge ? 0 : 1;
-    const int count = num + (isEdge ? 0 : 2);
+float *afx_auditory_edges(int num, int fftLength, int samplate, SpectralFilterBankScaleType scale, float lowFre,
+                          float highFre, int binPerOctave, int isEdge, int *count) {
+    const int n = num + (isEdge ? 0 : 2);
     float ref = 0;
     ScaleFn fwd = id_map, inv = id_map;
 
@@ -350,6 +348,12 @@ int afx_auditory_bank(int num, int fftLength, int samplate, SpectralFilterBankSc
             afx_auditory_revise_log(num, lowFre, highFre, (int)ref, isEdge, &lowFre, &highFre);
             fwd = afx_fre_to_log;
             inv = afx_log_to_fre;
+            break;
+        case SpectralFilterBankScale_Linear: /* the bin grid (no caller of afx_auditory_bank passes this scale) */
+            ref = (float)(samplate * 1.0 / fftLength);
+            afx_auditory_revise_linear(num, lowFre, highFre, ref, isEdge, &lowFre, &highFre);
+            fwd = fre_to_linear;
+            inv = linear_to_fre;
             break;
         case SpectralFilterBankScale_Linspace:
             revise_linspace(num, lowFre, highFre, isEdge, &lowFre, &highFre);
@@ -377,14 +381,28 @@ int afx_auditory_bank(int num, int fftLength, int samplate, SpectralFilterBankSc
 
     /* 1. band edges: equally spaced on the scale axis, mapped back to Hz, then
      *    to FFT bins (auditory_filterBank.c:594-677) */
-    float *fre = afx_linspace(fwd(lowFre, ref), fwd(highFre, ref), count, 0);
+    float *fre = afx_linspace(fwd(lowFre, ref), fwd(highFre, ref), n, 0);
+    if (!fre) return NULL;
+    for (int i = 0; i < n; i++) fre[i] = inv(fre[i], ref);
+    if (count) *count = n;
+    return fre;
+}
+
+int afx_auditory_bank(int num, int fftLength, int samplate, SpectralFilterBankScaleType scale,
+                       SpectralFilterBankStyleType style, SpectralFilterBankNormalType normal,
+                       float lowFre, float highFre, int binPerOctave, float *bank, float *freOut,
+                       int *binOut) {
+    const int isEdge = (style == SpectralFilterBankStyle_Gammatone);
+    const int offset = isEdge ? 0 : 1;
+    const int count = num + (isEdge ? 0 : 2);
+    /* 0./1. band edges in Hz, then FFT bins (auditory_filterBank.c:82-119, :594-677) */
+    float *fre = afx_auditory_edges(num, fftLength, samplate, scale, lowFre, highFre, binPerOctave, isEdge, NULL);
     int *bin = (int *)calloc((size_t)num + 2, sizeof(int));
     if (!fre || !bin) {
         free(fre);
         free(bin);
         return AFX_ERR_NOMEM;
     }
-    for (int i = 0; i < count; i++) fre[i] = inv(fre[i], ref);
     if (style != SpectralFilterBankStyle_Slaney) {
         for (int i = 0; i < count; i++) bin[i] = (int)roundf(fftLength * fre[i] / samplate);
     } else { /* first grid point strictly above the edge frequency */

@@ -37,6 +37,11 @@ void afx_auditory_revise_linear(int num, float lowFre, float highFre, float detF
                                 float *lowOut, float *highOut);
 void afx_auditory_revise_log(int num, float lowFre, float highFre, int binPerOctave, int isEdge,
                              float *lowOut, float *highOut);
+/* the band edges every auditory bank starts from (auditory_filterBank.c:82-119, :594-677): [low, high] widened by one
+ * band on each side (isEdge 0; the linear scale snaps to the bin grid first), num + 2 points (isEdge 0) or num (isEdge 1)
+ * equally spaced on the scale's axis, mapped back to Hz.  malloc'ed, *count entries; NULL: out of memory */
+float *afx_auditory_edges(int num, int fftLength, int samplate, SpectralFilterBankScaleType scale, float lowFre,
+                          float highFre, int binPerOctave, int isEdge, int *count);
 float afx_fre_to_log(float fre, float binPerOctave);
 float afx_log_to_fre(float value, float binPerOctave);
 

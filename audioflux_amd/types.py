@@ -119,3 +119,8 @@ class ReassignType(IntEnum):
     FRE = 1
     TIME = 2
     NONE = 3
+
+
+class NSGTFilterBankType(IntEnum):
+    EFFICIENT = 0
+    STANDARD = 1

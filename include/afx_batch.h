@@ -32,6 +32,7 @@
 #include "feature/xxcc_algorithm.h"
 #include "mir/hpss_algorithm.h"
 #include "mir/_pitch_yin.h"
+#include "nsgt_algorithm.h"
 #include "pwt_algorithm.h"
 #include "reassign_algorithm.h"
 #include "spectrogram_algorithm.h"
@@ -279,6 +280,17 @@ int pitchYINObj_curveBatchDevice(PitchYINObj pitchYINObj, const float *dData, in
                                  float *dYin, void *hipStream);
 int pitchYINObj_yinLength(PitchYINObj pitchYINObj);
 int pitchYINObj_minIndex(PitchYINObj pitchYINObj);
+
+/* ---- NSGT (nsgt_algorithm.h declares nsgtObj_nsgtBatchDevice beside the object) -----------------------------------------
+ * The plan nsgtObj_new would build for the same parameters, on the host and WITHOUT a device (tests, float64 references):
+ * lengthArr / offsetArr / binArr / freArr [num], windowArr [totalLength] (band after band), colMapArr [num][maxLength] (the
+ * cell index each matrix column holds); every array may be NULL -- call once without windowArr / colMapArr to learn
+ * *maxLength and *totalLength.  Returns what nsgtObj_new returns for the parameters (0, -100, 1, -1, -4, -5). */
+int afx_nsgt_plan_host(int num, int radix2Exp, int *samplate, float *lowFre, float *highFre, int *binPerOctave,
+                       int *minLength, NSGTFilterBankType *nsgtFilterBankType,
+                       SpectralFilterBankScaleType *filterScaleType, SpectralFilterBankStyleType *filterStyleType,
+                       SpectralFilterBankNormalType *filterNormalType, int *lengthArr, int *offsetArr, int *binArr,
+                       float *freArr, float *windowArr, int *maxLength, int *totalLength, int *colMapArr);
 
 #ifdef __cplusplus
 }
