@@ -634,6 +634,47 @@ int afxk_nsgt_spectrum(const AfxCwtPlanDims *d, const float *tw, const float *x,
  * launch limits (chunks > 65535). */
 int afxk_nsgt_bands(const AfxNsgtArgs *a, void *stream);
 
+/* ---- harmonic product / log-harmonic sum pitch tracking (afx_pitch_hs.hip) -- */
+#define AFX_PITCH_HPS 0 /* curve[j] = prod_k |X[j (k + 1)]|     */
+#define AFX_PITCH_LHS 1 /* curve[j] = sum_k log |X[j (k + 1)]| */
+#define AFX_PITCH_HS_LDS_BUDGET (160 * 1024) /* LDS one workgroup may declare on gfx950 */
+#define AFX_PITCH_HS_SCRATCH_GROUPS 1024     /* workgroups of a launch whose spectrum slice lives in device scratch */
+/* floats of a spectrum slice that holds bins 0 ... lastBin: one float of padding per 32 keeps the stride M / fftLength of
+ * a residue's bins off a single LDS bank */
+static inline long long afx_pitch_hs_slice_floats(long long lastBin) { return lastBin + (lastBin >> 5) + 1; }
+/* LDS bytes of a workgroup without the slice: cross-wave exchange, transform buffer (afx_ldsfft.h padding), windowed frame */
+static inline long long afx_pitch_hs_lds_fixed(int radix2Exp) {
+    const long long n = 1LL << radix2Exp;
+    return 128 + 8 * (n + (n >> 5) + 1) + 4 * n;
+}
+typedef struct {
+    const float *x;        /* device, clip b starts at x + b * clipStride                                         */
+    long long clipStride;  /* in samples                                                                          */
+    int batch, dataLength; /* clips, samples per clip                                                             */
+    int timeLength;        /* frames per clip: (dataLength - fftLength) / hop + 1 > 0                             */
+    int kind;              /* AFX_PITCH_HPS / AFX_PITCH_LHS                                                       */
+    int radix2Exp, hop;    /* fftLength = 2^radix2Exp, 6 ... 13; hop > 0 (may exceed fftLength)                   */
+    int interpExp;         /* M = 2^interpExp >= fftLength: the zero-padded transform length                      */
+    int minIndex, maxIndex; /* candidates: 0 <= minIndex <= maxIndex                                              */
+    int harmonicCount;     /* >= 1, maxIndex * harmonicCount < M                                                  */
+    double freStep;        /* 1.0 * samplate / M                                                                  */
+    const float *window;   /* device [fftLength]                                                                  */
+    const float *twiddle;  /* device float2 (cos, -sin)(2 pi m / fftLength), m < fftLength / 2                    */
+    const float *roots;    /* device float2 (cos, -sin)(2 pi m / M), m < M                                        */
+    float *slice;          /* device scratch [groups][afx_pitch_hs_slice_floats(maxIndex * harmonicCount)], or NULL:
+                            * the slice lives in LDS                                                              */
+    int groups;            /* workgroups of the launch when slice != NULL (<= AFX_PITCH_HS_SCRATCH_GROUPS)        */
+    float *fre, *value;    /* device [b * outStride + t] or NULL                                                  */
+    long long outStride;
+    float *curve;          /* device [row * (maxIndex + 1) + j], row = b * timeLength + t, or NULL                */
+} AfxPitchHsArgs;
+/* One launch from samples to results (_pitch_hps.c:415-518, _pitch_lhs.c:416-532): window, the needed bins of the
+ * M-point spectrum of the zero-padded frame as M / fftLength modulated fftLength-point transforms in LDS (half of them:
+ * the frame is real), the harmonic product / log-sum over 0 ... maxIndex, the first argmax over minIndex ... maxIndex.
+ * One workgroup per frame (a fixed number of workgroups striding over the frames when the slice lives in scratch).
+ * AFX_ERR_ARG for a plan outside the limits above, AFX_ERR_UNSUPPORTED beyond 2^31 - 1 frames in a launch. */
+int afxk_pitch_hs(const AfxPitchHsArgs *a, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,30 @@ struct OpaquePitchYIN {
     int status;
 };
 
+/* the harmonic-product-spectrum and log-harmonic-sum pitch trackers (afx_pitch_hs.c, mir/_pitch_hps.h, mir/_pitch_lhs.h):
+ * one layout, `kind` selects the combining operator */
+struct OpaquePitchHS {
+    int kind;                /* AFX_PITCH_HPS / AFX_PITCH_LHS */
+    int radix2Exp, fftLength, slideLength;
+    int samplate, interpLength, interpExp; /* M = 2^interpExp: the zero-padded transform the reference runs per frame */
+    int minIndex, maxIndex, harmonicCount;
+    int lastBin;             /* maxIndex * harmonicCount: the highest bin of the M-point spectrum a curve reads */
+    int sliceInLds;          /* the spectrum slice fits in LDS beside the transform buffer and the frame */
+    int transforms;          /* fftLength-point transforms per frame */
+    WindowType windowType;
+    int isDebug;
+    AfxFrameTail tail;       /* isContinue and the samples carried between host-pointer calls */
+    int timeLength;          /* frames of the last pitch call */
+    void *stream;
+    float *dWindow, *dTwiddle, *dRoots;
+    float *dSlice;           /* grow-only: [groups][slice floats] of the plans whose slice does not fit in LDS */
+    size_t capSlice;
+    float *dX, *dOut;        /* grow-only device buffers of the host-pointer call: samples, [T] */
+    size_t capX, capOut;
+    AfxScratchStream scratchStream;
+    int status;
+};
+
 /* validated parameters of a BFT execution plan (afx_bft.c) */
 typedef struct {
     int num, radix2Exp, samplate;
