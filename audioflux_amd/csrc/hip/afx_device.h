@@ -675,6 +675,50 @@ typedef struct {
  * AFX_ERR_ARG for a plan outside the limits above, AFX_ERR_UNSUPPORTED beyond 2^31 - 1 frames in a launch. */
 int afxk_pitch_hs(const AfxPitchHsArgs *a, void *stream);
 
+/* ---- pitch-estimation-filter tracking (afx_pitch_pef.hip) ------------------- */
+#define AFX_PITCH_PEF_MIN_EXP 6
+#define AFX_PITCH_PEF_MAX_EXP 12 /* 13: 167 KB of LDS for a plan that reads every bin, above the 160 KB of a gfx950 CU */
+/* one entry of the log grid: y[m] = (index < 0 ? pw[N] : pw[index] + dx * (pw[index + 1] - pw[index]) / dl) * bw, the
+ * operands of __vinterp_linear (flux_vectorOp.c:580-610) precomputed in float32 */
+typedef struct __attribute__((aligned(16))) { /* one 16-byte load */
+    int index;  /* 0 ... N - 1, or -1: past the last linear frequency */
+    float dx;   /* lg[m] - lin[index]            */
+    float dl;   /* lin[index + 1] - lin[index]   */
+    float bw;   /* bandWidthArr[m]               */
+} AfxPitchPefTap;
+/* LDS bytes of a workgroup: cross-wave exchange, the 2N-point complex transform buffer (afx_ldsfft.h padding), and the
+ * pwLength <= N + 1 bins of the power spectrum the log grid reads (rounded up to 16 bytes) */
+static inline long long afx_pitch_pef_lds_bytes(int radix2Exp, int pwLength) {
+    const long long n = 1LL << radix2Exp;
+    return 128 + 8 * (2 * n + (2 * n >> 5) + 1) + 4 * (((long long)pwLength + 3) & ~3LL);
+}
+typedef struct {
+    const float *x;        /* device, clip b starts at x + b * clipStride                                         */
+    long long clipStride;  /* in samples                                                                          */
+    int batch, dataLength; /* clips, samples per clip                                                             */
+    int timeLength;        /* frames per clip: (dataLength - fftLength) / hop + 1 > 0                             */
+    int radix2Exp, hop;    /* N = fftLength = 2^radix2Exp, 6 ... 12; hop > 0 (may exceed fftLength)               */
+    int minIndex, maxIndex; /* candidates: 0 <= minIndex <= maxIndex < 2N                                         */
+    int filterPadNum;      /* 0 ... N: zeros in front of the log spectrum                                         */
+    int pwLength;          /* bins 0 ... pwLength - 1 of the power spectrum are kept: every taps[m].index + 2 <=
+                            * pwLength <= N + 1, and N + 1 when an index is -1                                    */
+    const float *window;   /* device [N]                                                                          */
+    const float *twiddle;  /* device float2 (cos, -sin)(2 pi m / 4N), m < 2N                                      */
+    const AfxPitchPefTap *taps; /* device [2N], 16-byte aligned                                                   */
+    const float *filterSpec; /* device float2 [2N + 1]: conj of the 4N-point spectrum of h, bins 0 ... 2N, times 1 / 2N */
+    const float *lg;       /* device [2N]: the log frequencies                                                    */
+    float *fre, *value;    /* device [b * outStride + t] or NULL                                                  */
+    long long outStride;
+    float *curve;          /* device [row * (maxIndex + 1) + k], row = b * timeLength + t, or NULL                */
+} AfxPitchPefArgs;
+/* One launch from samples to results (_pitch_pef.c:258-426): window, power spectrum of the frame zero-padded to 2N points
+ * (an N-point complex transform and the real split), interpolation onto the log grid, the correlation with the filter as
+ * a 4N-point real one (two 2N-point complex transforms around a product with filterSpec), the first argmax over
+ * minIndex ... maxIndex.  Workgroups stride over the (clip, frame) rows; everything between the samples and the outputs
+ * stays in LDS and registers.  AFX_ERR_ARG for a plan outside the limits above, AFX_ERR_UNSUPPORTED beyond 2^31 - 1 frames
+ * in a launch. */
+int afxk_pitch_pef(const AfxPitchPefArgs *a, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -183,6 +183,23 @@ struct OpaquePitchHS {
     int status;
 };
 
+/* the pitch-estimation-filter tracker (afx_pitch_pef.c, mir/_pitch_pef.h) */
+struct OpaquePitchPEF {
+    int radix2Exp, fftLength, slideLength, samplate;
+    int minIndex, maxIndex, filterPadNum;
+    int pwLength;            /* bins of the power spectrum the log grid reads */
+    float lowFre, highFre, cutFre, alpha, beta, gamma;
+    WindowType windowType;
+    int isDebug;
+    AfxFrameTail tail;       /* isContinue and the samples carried between host-pointer calls */
+    int timeLength;          /* frames of the last pitch call */
+    void *stream;
+    float *dWindow, *dTwiddle, *dTaps, *dFilterSpec, *dLg; /* uploaded once: [N], [4N], [2N] taps, [2N + 1] float2, [2N] */
+    float *dX, *dOut;        /* grow-only device buffers of the host-pointer call: samples, [T] */
+    size_t capX, capOut;
+    int status;
+};
+
 /* validated parameters of a BFT execution plan (afx_bft.c) */
 typedef struct {
     int num, radix2Exp, samplate;
