@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <afx_asm.h>
+#include <afx_frameops.h>
 
 // knock-out measurement builds of the block (make EXTRA=-DAFX_KO_CC=<mask>; results WRONG, timing only; profiles/r06_ab_mfcc.txt):
 // bit 0 the row loads (registers as they are), 1 the MFMAs (one v_add per product), 2 the rectification, 3 the wait for the stores
@@ -32,7 +33,8 @@ typedef float ccb_v4 __attribute__((ext_vector_type(4)));
 // instructions and, inlined into the frame loops, their registers)
 __device__ __forceinline__ float ccb_rect(float x, int cbrt) {
     constexpr float LOG10_2 = 0.30102999566398120f;
-    const float lg = __log2f(cbrt ? x : fmaxf(x, 1e-8f));
+    // (max_floor: one v_max_f32; a NaN row value -- always a quiet one, it is a result of arithmetic -- gives 1e-8 as with fmaxf)
+    const float lg = __log2f(cbrt ? x : max_floor(x));
     return cbrt ? __builtin_amdgcn_exp2f(lg * (float)(1.0 / 3)) : lg * LOG10_2;
 }
 
@@ -129,11 +131,14 @@ __device__ __forceinline__ void ccb_rows(const float *out, float *cc, const floa
     }
     const ccb_v4 sum = CHAINS == 4 ? (acc[0] + acc[1]) + (acc[2 % CHAINS] + acc[3 % CHAINS]) : acc[0] + acc[1];
     // C layout: column (coefficient) = lane & 15, row (frame) = 4 (lane >> 4) + reg
+    // (one wave-uniform base per register + one lane offset: no 64-bit address per lane and store)
     if (dOn) {
+        const unsigned vcc = 4u * (unsigned)(4 * g * ccNum + fi);
+        float *const scc = reinterpret_cast<float *>(uniform64(reinterpret_cast<long long>(cc + fb * ccNum)));
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const int rr = 4 * g + reg;
-            if (rr < cnt) cc[(fb + rr) * ccNum + fi] = sum[reg];
+            if (rr < cnt) GST32_S(vcc, sum[reg], scc + reg * ccNum);
         }
     }
 }

@@ -43,8 +43,10 @@
 // cepstrum block (16: one full MFMA tile; 8: the rows are half as old when they are re-read)
 #ifdef AFX_V2_NTIN
 #define AFX_V2_LOAD(p) __builtin_nontemporal_load(p)
+#define AFX_V2_NT true   // (the hand-issued fetch of the new rows, rows_fetch_new_s, takes the policy as a template argument)
 #else
 #define AFX_V2_LOAD(p) (*(p))
+#define AFX_V2_NT false
 #endif
 #ifndef AFX_V2_CCEVERY
 #define AFX_V2_CCEVERY 16
@@ -231,6 +233,13 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
     const unsigned seg0 = SPLIT ? (unsigned)a.meta[256 + lane] : 0u, seg1 = SPLIT ? (unsigned)a.meta[320 + lane] : 0u;
     const unsigned apa = R + 4 * startA, apb = R + 4 * startB;
     const unsigned awr = T0 + T_BAND + 4 * WP * lane;
+    // global memory, per lane and loop-invariant: byte offsets from wave-uniform (scalar) bases -- the frame loop forms no 64-bit
+    // address on the vector unit.  vRaw: the lane's float2 in a 512-byte row of samples; vRowA / vRowB: its two bank rows' slots
+    // in an output row (okA / okB: the lane has such a row); rowPitch: floats from one output row to the next
+    const unsigned vRaw = 8u * (unsigned)lane, vLane = 4u * (unsigned)lane;
+    const bool okA = rowA >= 0, okB = rowB >= 0;
+    const unsigned vRowA = okA ? 4u * (unsigned)rowA : 0u, vRowB = okB ? 4u * (unsigned)rowB : 0u;
+    const long long rowPitch = STFT ? a.outPitch : (long long)a.num;
 
     // ---- frame runs: no wave owns a share of the workgroup's range [wgBeg, wgBeg + wgN) -- a wave that runs out of frames claims
     //      the next run from the counter in LDS (lane 0: fetch-add; the length from a read just before it, which may be stale:
@@ -296,12 +305,25 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
         }
     };
 
+    // the next frame's new rows were requested by hand behind the first radix-16 (rows_fetch_new_s): they landed long ago,
+    // and they are waited for where the wait cannot meet a store that was issued a moment ago -- before the frame's row stores
+    // (k_stft_band_4k2 does the same).  The registers' first use is pinned behind the wait
+    auto raw_landed = [&]() {
+        if constexpr (SHIFT > 0) {
+            VM_WAIT_ALL();
+#pragma unroll
+            for (int n1 = 0; n1 < 16; ++n1) PIN(raw[n1]);
+        }
+    };
+
     // ---- cepstra of `cnt` (<= 16) consecutive rows fb.. of this wave: C[16 frames, 16 coefficients] =
     //      log10(max(rows, 1e-8)) . D^T with v_mfma_f32_16x16x4_f32.  Lane (fi = lane & 15, g = lane >> 4)
     //      loads float4 row[fb + fi][16 u + 4 g ..] (k-slot g of MFMA (u, c) stands for band 16 u + 4 g + c),
     //      the matching DCT elements come from the LDS table.  Called one frame AFTER the 16th row was
     //      stored, so the s_waitcnt finds those stores long complete; reads bypass the CU's L1.
-    auto cc_block = [&](long long fb, int cnt) {
+    // fb: the first row's frame per lane (CC == 2); fbS: the same number, wave-uniform, from the run's scalar row offset / 128
+    // (CC == 1, where num is 128; not used otherwise)
+    auto cc_block = [&](long long fb, long long fbS, int cnt) {
         if constexpr (CC == 2) {  // the general form: runtime num / rectification, DCT operand from memory
             ccb_rows<SPLIT ? 2 : 4>(a.out, a.cc, a.dct, a.num, a.ccNum, a.ccCbrt, fb, cnt, lane);
         } else {
@@ -309,8 +331,10 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
         int ln = lane;
         PIN(ln);  // keep this block's per-lane values out of the frame loop's registers
         const int fi = ln & 15, g = ln >> 4;
-        const long long r = fb + (fi < cnt ? fi : cnt - 1);  // tail: duplicate the last row, not stored
-        const v4f *src = reinterpret_cast<const v4f *>(a.out + r * 128) + g;
+        // row fb + fi (tail: duplicate the last row, not stored), bands 4 g ..: one scalar base + this lane offset + immediates
+        fbS = uniform64(fbS);  // (the run's last block is reached under a per-lane condition: say that the number is the wave's)
+        const float *const srows = a.out + fbS * 128;
+        const unsigned vsrc = 512u * (unsigned)(fi < cnt ? fi : cnt - 1) + 16u * (unsigned)g;
         const unsigned ad = T0 + TABB + 4 * DCT_PITCH * ln;
         v4f acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
         constexpr float LOG10_2 = 0.30102999566398120f;
@@ -319,8 +343,8 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             v4f av[4], dv[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) LOAD_SC1_B128(av[u], src + 4 * (4 * h + u));  // served by the L2, never by this CU's L1
+            // (served by the L2, never by this CU's L1; bands 16 (4 h + u) + 4 g ..: 64 (4 h + u) bytes)
+            GLD128X4_L2_S(av[0], av[1], av[2], av[3], vsrc, srows, 256 * h, 256 * h + 64, 256 * h + 128, 256 * h + 192);
 #pragma unroll
             for (int u = 0; u < 4; ++u) RD128(dv[u], ad, 16 * (4 * h + u));
             VM_LGKM_WAIT_ALL();
@@ -330,11 +354,12 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
             for (int u = 0; u < 4; ++u) PIN(dv[u]);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
+                const v4f fl = max4_floor(av[u]);  // one v_max_f32 per value; a NaN row value gives 1e-8 as with fmaxf (afx_frameops.h)
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     // log10f(max(x, 1e-8)) (xxcc_algorithm.c:131-137) as v_log_f32 * log10(2); four
                     // independent accumulator chains (a dependent f32 MFMA waits 40 cycles)
-                    const float lg = __log2f(fmaxf(av[u][c], 1e-8f)) * LOG10_2;
+                    const float lg = __log2f(fl[c]) * LOG10_2;
                     acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(lg, dv[u][c], acc[c], 0, 0, 0);
                 }
             }
@@ -342,10 +367,12 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
         const v4f sum = (acc[0] + acc[1]) + (acc[2] + acc[3]);
         // C layout: column (coefficient) = lane & 15, row (frame) = 4 (lane >> 4) + reg
         if (fi < a.ccNum) {
+            const unsigned vcc = 4u * (unsigned)(4 * g * a.ccNum + fi);
+            float *const scc = a.cc + fbS * a.ccNum;
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) {
                 const int rr = 4 * g + reg;
-                if (rr < cnt) a.cc[(fb + rr) * a.ccNum + fi] = sum[reg];
+                if (rr < cnt) GST32_S(vcc, sum[reg], scc + reg * a.ccNum);
             }
         }
         }  // CC == 1
@@ -367,6 +394,7 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
     int clip, t;
     locate(fClaim, clip, t);
     fetch(a.x + (long long)clip * a.clipStride + (long long)t * a.hop, 0);
+    long long rowOff = fClaim * rowPitch;  // floats from the output's start to frame f's row: wave-uniform, advanced per frame
     for (; f < fEnd; ++f) {
         v2 v[16];
         MEL_PHASE(0);
@@ -389,24 +417,6 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
                 v[2 * j] = raw[2 * j] * lo2(wv[j]);
                 v[2 * j + 1] = raw[2 * j + 1] * hi2(wv[j]);
             }
-        }
-        // ---- 1b. start fetching the next frame: in flight under the whole transform ---------
-        if (f + 1 < fEnd) {
-            int tn = t + 1, cn = clip;
-            if (tn == a.timeLength) {
-                tn = 0;
-                ++cn;
-            }
-            const float *pn = a.x + (long long)cn * a.clipStride + (long long)tn * a.hop;
-            bool whole = true;
-            if constexpr (SHIFT > 0) {
-                if (tn != 0) {
-                    shift_rows_inplace<SHIFT>(raw);  // (in place: afx_asm.h)
-                    fetch(pn, 16 - SHIFT);
-                    whole = false;
-                }
-            }
-            if (whole) fetch(pn, 0);
         }
         // ---- 1c. temporal features of the windowed frame (temporal_algorithm.c:138-144) -------
         if constexpr (TEMPORAL) {
@@ -453,6 +463,44 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
                 const unsigned b = aE1w + 2304 * g;  // rows 4g .. 4g+3, 576 bytes = 72 units apart
                 WR2_64_S(0, b, o[4 * g], o[4 * g + 1], 0, 72);
                 WR2_64_S(0, b, o[4 * g + 2], o[4 * g + 3], 144, 216);
+            }
+        }
+        // ---- 1b. start fetching the next frame: in flight under the rest of the transform.  Behind the first radix-16 and its
+        //      exchange writes (only hand-issued instructions stand between: the compiler's arithmetic is not cut in two), not
+        //      in front of it: the compiler folds the window products of rows 0 .. 7 into the first butterflies (fma: these are the
+        //      bits every result has had since round 2), so the image is read until then -- moved in place before its last
+        //      use, the compiler kept the old image beside the new one and copied it, 16 v_mov_b64 per frame
+        if (f + 1 < fEnd) {
+            int tn = t + 1, cn = clip;
+            if (tn == a.timeLength) {
+                tn = 0;
+                ++cn;
+            }
+            const float *pn = a.x + (long long)cn * a.clipStride + (long long)tn * a.hop;
+            bool whole = true;
+            if constexpr (SHIFT > 0) {
+                if (tn != 0) {
+                    // in place; aligned frames: the SHIFT new rows are requested by hand from the scalar address of row
+                    // 16 - SHIFT (afx_frameops.h) and waited for by hand before this frame's row stores
+                    shift_rows_inplace<SHIFT>(raw);  // (afx_asm.h)
+                    if (a.aligned) {
+                        rows_fetch_new_s<SHIFT, AFX_V2_NT>(raw, vRaw, pn + 128 * (16 - SHIFT));
+                    } else {
+                        // (nothing is in flight here -- this frame's hand-issued loads are in the other arm, the last frame's
+                        //  were waited for before its row stores -- but the compiler uses the image's registers for this arm's
+                        //  addresses, and the linear scan of tests/test_isa_forms.py reads the arms one after the other: the
+                        //  wait says so there, and costs nothing; the addresses are formed behind it: they have its zero added)
+                        int z = 0;
+                        VM_WAIT_ALL_AT(z);
+                        fetch(pn + z, 16 - SHIFT);
+                    }
+                    whole = false;
+                }
+            }
+            if (whole) {
+                int z = 0;
+                if constexpr (SHIFT > 0) VM_WAIT_ALL_AT(z);  // (as above)
+                fetch(pn + z, 0);
             }
         }
         wave_lds_sync();
@@ -598,7 +646,8 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
         if constexpr (STFT) {
             // ---- 4'. the row itself: 16-byte reads of the natural-order row, 1 KB per store instruction of the wave ----
             MEL_PHASE(6);
-            float *orow = a.out + f * a.outPitch;
+            raw_landed();
+            float *orow = a.out + rowOff;
             if (a.vecOut) {
                 const float4 *p4 = reinterpret_cast<const float4 *>(prow);
                 float4 *o4 = reinterpret_cast<float4 *>(orow);
@@ -629,10 +678,11 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
         }
         MEL_PHASE(6);
         // ---- 5. store (first the cepstra of the 16 rows stored before this one, if that many wait) ----
+        if (pass == 0) raw_landed();  // (in front of the cepstrum block's own wait and of the row stores)
         if constexpr (CC != 0 && !SPLIT) {
-            if (ccN == AFX_V2_CCEVERY) cc_block(f - AFX_V2_CCEVERY, AFX_V2_CCEVERY);
+            if (ccN == AFX_V2_CCEVERY) cc_block(f - AFX_V2_CCEVERY, (rowOff >> 7) - AFX_V2_CCEVERY, AFX_V2_CCEVERY);
         }
-        float *orow = ((CPLX && pass) ? a.outIm : a.out) + f * a.num;
+        float *const srow = ((CPLX && pass) ? a.outIm : a.out) + rowOff;  // wave-uniform
         if constexpr (SPLIT) {
             // slot results -> LDS (start of the wave's region: the image there is dead since stage 3),
             // then every row is the sum of its segments in ascending bins
@@ -649,18 +699,18 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
                 sum += part[(u >> 16) & 255u];
                 sum += part[u >> 24];
                 if (!CPLX && a.postPow) sum = powf(sum, a.normValue);
-                if (lane + 64 * h < a.num) orow[lane + 64 * h] = sum;
+                if (lane + 64 * h < a.num) GST32_S(vLane, sum, srow + 64 * h);
             }
         } else {
-            if (rowA >= 0) orow[rowA] = accA;
-            if (rowB >= 0) orow[rowB] = accB;
+            if (okA) GST32_S(vRowA, accA, srow);
+            if (okB) GST32_S(vRowB, accB, srow);
         }
         if constexpr (CC != 0) {
             ++ccN;
             // the wave's last rows (drains its last stores).  Split plans: ONE call site, behind the row's stores where the
             // band stage's values are dead (beside them the block spilled 336-656 bytes per lane); its wait then covers the
             // stores of the 16th row as well, once per 16 frames
-            if (f + 1 == fEnd || (SPLIT && ccN == 16)) cc_block(f + 1 - ccN, ccN);
+            if (f + 1 == fEnd || (SPLIT && ccN == 16)) cc_block(f + 1 - ccN, (rowOff >> 7) + 1 - ccN, ccN);
         }
         }  // !STFT
         wave_lds_sync();  // the next frame overwrites the images / the power row
@@ -671,6 +721,7 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
         ++stampN;
         if (lane0 && (stampN & 15) == 0 && STAMP_HEAD + (stampN >> 4) <= STAMP_WORDS) stamp[STAMP_HEAD - 1 + (stampN >> 4)] = __builtin_amdgcn_s_memtime();
 #endif
+        rowOff += rowPitch;
         if (++t == a.timeLength) {
             t = 0;
             ++clip;

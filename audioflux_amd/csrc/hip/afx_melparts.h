@@ -1,6 +1,7 @@
 // afx_melparts.h -- device pieces shared by the fused STFT -> filter-bank kernels (afx_melfused{512,1k,2,4k2}.hip): one
 // definition each.  The wave transforms, the frame loops and the power-row layouts stay in their files; what is here is what
-// those files had word for word.  Only what both afx_asm.h and its host stand-in (tests/emu/hip/afx_asm.h) provide is used.
+// those files had word for word.  Only what both afx_asm.h and its host stand-in (tests/emu/hip/afx_asm.h) provide is used,
+// and afx_frameops.h, which carries its own C twins for the emulated builds.
 // (stft_map, which the STFT kernels without hand-issued LDS accesses share too, is in afx_pkmath.h.)
 #ifndef AFX_MELPARTS_H
 #define AFX_MELPARTS_H
@@ -9,6 +10,7 @@
 
 #include "afx_device.h"
 #include "afx_pkmath.h"
+#include "afx_frameops.h"
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ v2 lo2(v4f q) { return v2{q.x, q.y}; }
@@ -28,10 +30,9 @@ __device__ __forceinline__ void split_pair(v2 A, v2 B, v2 w, float &pk, float &p
     const v2 e2 = pk_add_conj(A, B);   // 2 E
     const v2 d = pk_sub_conj(A, B);    // 2 i O
     const v2 wo = cmul_mi(d, w);       // W O
-    const v2 x = e2 * 0.5f + wo;       // X[k]
-    const v2 y = e2 * 0.5f - wo;       // conj(X[M - k])
-    pk = x.x * x.x + x.y * x.y;
-    pq = y.x * y.x + y.y * y.y;
+    const v2 p = pair_power(e2, wo);   // (|x|^2, |y|^2) of x = e2 / 2 + wo = X[k], y = e2 / 2 - wo = conj(X[M - k]) (afx_frameops.h)
+    pk = p.x;
+    pq = p.y;
 }
 // complex results: the spectrum values themselves, x = X[k], y = conj(X[M - k])
 __device__ __forceinline__ void split_pair_c(v2 A, v2 B, v2 w, v2 &x, v2 &y) {
