@@ -719,6 +719,40 @@ typedef struct {
  * in a launch. */
 int afxk_pitch_pef(const AfxPitchPefArgs *a, void *stream);
 
+/* ---- onset detection (afx_onset.hip) ---------------------------------------- */
+/* frames of one clip's envelope the picker keeps in LDS (32 KB: four workgroups of a CU keep theirs); a longer clip is
+ * picked from global memory (the envelope the same workgroup wrote, or the caller's) */
+#define AFX_ONSET_LDS_FRAMES 8192
+/* floats of a tile of whole rows the max filter keeps in LDS; a longer row is filtered from global memory (its second
+ * read finds it in L2) */
+#define AFX_ONSET_FILTER_TILE 2048
+/* out[r, j] = max of in[r, max(j - order / 2, 0) ... min(j - 1 + order - order / 2, cols - 1)] (__vmaxfilter,
+ * flux_vector.c:3063-3081), order >= 1 (any size: the window is cut at the row's ends); in != out.  Exact. */
+int afxk_max_filter(const float *in, long long rows, int cols, int order, float *out, void *stream);
+typedef struct {
+    const float *src;      /* device: clip b's values at src + b * srcStride                                      */
+    long long srcStride;
+    int batch, length;     /* clips, frames per clip (> 0)                                                        */
+    int normalise;         /* 1: e = src - min(src), then e / max(e) when that is > 0 (onset_algorithm.c:379-385),
+                            * stored to evn; 0: e = src                                                           */
+    float *evn;            /* device [b * evnStride + t], normalise only                                          */
+    long long evnStride;
+    int preMax, postMax, preAvg, postAvg, wait; /* preMax, preAvg, wait >= 0; postMax, postAvg >= 1               */
+    float delta;
+    int *point;            /* device [b * pointStride + k] or NULL: the first pointStride points of a clip        */
+    int *count;            /* device [b] or NULL: all points of the clip                                          */
+    long long pointStride;
+} AfxOnsetPickArgs;
+/* One workgroup per clip, one launch: (min, max, normalise,) the candidates of __peakPick (onset_algorithm.c:423-460) --
+ * e[i] == max of its window, e[i] >= float32 mean of its window summed in index order + delta -- per tile of frames in
+ * parallel, compacted in order, and the wait rule over the candidates alone.  AFX_ERR_ARG outside the limits above. */
+int afxk_onset_pick(const AfxOnsetPickArgs *a, void *stream);
+/* out[b * stride + i] = max(10 log10f(in[b * stride + i] / max_i in[b * stride + i]), min), i < length
+ * (util_powerToDB, flux_util.c:549-571; min as given: the caller applied the >= 0 -> -80 rule): partial maxima of every
+ * clip (at most 32 per clip, in stream-ordered scratch that is released on the stream), then the map.  in == out
+ * allowed. */
+int afxk_power_to_db(const float *in, int batch, long long length, long long stride, float min, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

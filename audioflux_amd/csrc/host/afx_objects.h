@@ -200,6 +200,27 @@ struct OpaquePitchPEF {
     int status;
 };
 
+/* the onset detector (afx_onset.c, mir/onset_algorithm.h) */
+struct OpaqueOnset {
+    int noveltyType;         /* taken unchecked: anything that is not a named kind runs flux */
+    int nLength, mLength, order;
+    int preMax, postMax, preAvg, postAvg, wait;
+    float delta;
+    int step;                /* of the last call (onsetObj_debug prints it) */
+    void *stream;
+    float *dFre;             /* [mLength] zeros: the descriptor launcher wants a frequency table, no novelty kind reads it */
+    int *hIndex, *dIndex;    /* the index table of the last call that brought one, host copy and device copy */
+    int indexLength;
+    size_t capIndex;
+    float *dFilt, *dRaw;     /* grow-only scratch: the filtered rows of a chunk of clips (order >= 2), the raw novelty */
+    size_t capFilt, capRaw;
+    float *dIn, *dPhase, *dEvn; /* grow-only device buffers of the host-pointer call */
+    int *dPoint;             /* [nLength + 1]: the points, then their count */
+    size_t capIn, capPhase, capEvn, capPoint;
+    AfxScratchStream scratchStream;
+    int status;
+};
+
 /* validated parameters of a BFT execution plan (afx_bft.c) */
 typedef struct {
     int num, radix2Exp, samplate;

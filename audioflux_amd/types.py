@@ -124,3 +124,18 @@ class ReassignType(IntEnum):
 class NSGTFilterBankType(IntEnum):
     EFFICIENT = 0
     STANDARD = 1
+
+
+class NoveltyType(IntEnum):
+    """the novelty function of Onset (include/mir/onset_algorithm.h)"""
+    FLUX = 0
+    HFC = 1
+    SD = 2
+    SF = 3
+    MKL = 4
+    PD = 5
+    WPD = 6
+    NWPD = 7
+    CD = 8
+    RCD = 9
+    BROADBAND = 10

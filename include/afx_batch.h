@@ -31,6 +31,7 @@
 #include "feature/spectral_algorithm.h"
 #include "feature/xxcc_algorithm.h"
 #include "mir/hpss_algorithm.h"
+#include "mir/onset_algorithm.h"
 #include "mir/_pitch_yin.h"
 #include "nsgt_algorithm.h"
 #include "pwt_algorithm.h"
@@ -259,6 +260,16 @@ int hpssObj_spectraBatchDevice(HPSSObj hpssObj, const float *dData, int batch, i
  * AFX_ERR_UNSUPPORTED (-4): even order or order > 255; AFX_ERR_ARG: bad pointers / sizes / axis. */
 int afx_medianFilterDevice(const float *dIn, long long rows, int cols, int framesPerClip, int axis, int order, float *dOut,
                            void *hipStream);
+
+/* ---- onset detection (mir/onset_algorithm.h declares onsetObj_onsetBatchDevice, afx_maxFilterDevice, afx_peakPickDevice and
+ * afx_powerToDbDevice beside the object; this header includes it) --------------------------------------------------------- */
+/* the pick parameters onsetObj_new derives (onset_algorithm.c:123-133), without a device: out = {preMax, postMax, preAvg,
+ * postAvg, wait}, *delta = 0.07f; samplate <= 0 -> 32000, slideLength < 1 -> 512.  The products are evaluated in double and
+ * floored as float, as the reference does.  AFX_ERR_ARG for a NULL `out`; delta may be NULL. */
+int afx_onset_plan_host(int samplate, int slideLength, int out[5], float *delta);
+/* util/flux_util.c:549-571: dArr[i] = max(10 log10f(pArr[i] / max_i pArr[i]), min); dArr NULL -> in place; min >= 0 -> -80.
+ * Host pointers; a failure is counted by afx_error_count(). */
+void util_powerToDB(float *pArr, int length, float min, float *dArr);
 
 /* ---- YIN pitch contours of clips that already live in HBM (mir/_pitch_yin.h) -------------------------------------------
  * batch clips of dataLength samples -> dFre / dTrough / dMin [b * outStride + t], t < pitchYINObj_calTimeLength(dataLength):
