@@ -9,6 +9,7 @@
 #include <cstdlib>
 
 #include "afx_melplan.h"
+#include "afx_bandpack.h"
 
 namespace {
 
@@ -36,7 +37,22 @@ void pack_band(const AfxBandPlan *band, int TA, int WP, float *wL, int *meta) {
     }
 }
 
+// AfxBandPack -> the lane-weight block wL [64][WP] (the lane's stream a | b | c) and meta[512]
+void pack_band3(const AfxBandPack *pk, int WP, float *wL, int *meta) {
+    for (int l = 0; l < 64; ++l) {
+        for (int t = 0; t < pk->slots; ++t) wL[(size_t)l * WP + t] = pk->w[(size_t)t * 64 + l];
+        for (int q = 0; q < 3; ++q) {
+            meta[64 * q + l] = pk->base[q][l];
+            meta[192 + 64 * q + l] = pk->row[q][l];
+        }
+        meta[384 + l] = pk->cont[1][l];
+        meta[448 + l] = pk->cont[2][l];
+    }
+}
+
 }  // namespace
+
+extern "C" int afxk_melfused_pack(const void *plan) { return plan ? static_cast<const AfxMelPlan *>(plan)->pack : 0; }
 
 extern "C" int afxk_melfused_variant(int radix2Exp, int tapsA, int tapsB) {
     const AfxMelSize *s = size_of(radix2Exp);
@@ -66,26 +82,45 @@ extern "C" int afxk_melfused_create(void **plan, int radix2Exp, const float *hWi
     if (variant < 0) return AFX_ERR_UNSUPPORTED;
     const AfxMelSize *s = size_of(radix2Exp);
     const int TA = s->variants[variant].tapsA, TB = s->variants[variant].tapsB;
-    const int WP = TA + TB + 4;
+    // a whole-row plan of the cheapest variant is re-packed where the size's kernel has a packed form that runs fewer tap slots
+    // (afx_bandpack_build declines otherwise); AFX_MEL_NOPACK=1, read here, keeps the plan as it came
+    AfxBandPack pk = {};
+    int pack = 0;
+    const char *nopack = getenv("AFX_MEL_NOPACK");
+    if (s->numPacks > 0 && variant == 0 && !(nopack && atoi(nopack) != 0) &&
+        afx_bandpack_build(band, s->packs, s->numPacks, s->rowCap, TA + TB, &pk) == 0) {
+        for (int i = 0; i < s->numPacks; ++i)
+            if (s->packs[i][0] == pk.taps[0] && s->packs[i][1] == pk.taps[1] && s->packs[i][2] == pk.taps[2]) pack = i + 1;
+        if (!pack) afx_bandpack_free(&pk);  // (a layout that is not the size's: the planner returns only what it was given)
+    }
+    const int WP = (pack ? pk.slots : TA + TB) + 4;
     const size_t bytes = (size_t)s->bandOff + (size_t)64 * WP * 4;
     AfxMelPlan *p = static_cast<AfxMelPlan *>(calloc(1, sizeof(AfxMelPlan)));
     float *tab = static_cast<float *>(calloc(bytes, 1));
     if (!p || !tab) {
         free(p);
         free(tab);
+        if (pack) afx_bandpack_free(&pk);
         return AFX_ERR_NOMEM;
     }
     p->radix2Exp = radix2Exp;
     p->variant = variant;
     p->num = band->num;
     p->split = band->split;
+    p->pack = pack;
     s->fill(tab, hWindow);
-    int meta[384];
-    pack_band(band, TA, WP, tab + s->bandOff / 4, meta);
+    int meta[512];
+    const size_t metaBytes = (pack ? 512 : 384) * sizeof(int);
+    if (pack) {
+        pack_band3(&pk, WP, tab + s->bandOff / 4, meta);
+        afx_bandpack_free(&pk);
+    } else {
+        pack_band(band, TA, WP, tab + s->bandOff / 4, meta);
+    }
     int st = afxdev_malloc(reinterpret_cast<void **>(&p->dTab), bytes);
     if (st == AFX_OK) st = afxdev_h2d(p->dTab, tab, bytes, stream);
-    if (st == AFX_OK) st = afxdev_malloc(reinterpret_cast<void **>(&p->dMeta), sizeof(meta));
-    if (st == AFX_OK) st = afxdev_h2d(p->dMeta, meta, sizeof(meta), stream);
+    if (st == AFX_OK) st = afxdev_malloc(reinterpret_cast<void **>(&p->dMeta), metaBytes);
+    if (st == AFX_OK) st = afxdev_h2d(p->dMeta, meta, metaBytes, stream);
     if (st == AFX_OK) st = afxdev_stream_sync(stream);  // host staging buffers are freed below
     free(tab);
     if (st != AFX_OK) {

@@ -79,12 +79,13 @@ constexpr int T_TW2 = 16384;                 // [4] rows of 16 float2, TW2_PITCH
 constexpr int TW2_PITCH = 144;               // (128 put rows m2 and m2 + 2 on the same banks: every read of this table two-way
                                              //  conflicted -- the 6.4 % of the kernel's LDS cycles SQ_LDS_BANK_CONFLICT showed)
 constexpr int T_TW3 = 16960;                 // [2][64][4] float2: 0.5 W_2048^bin of slot (s, lane, m)
-constexpr int T_BAND = 21056;                // [64][WP] floats: lane-major band weights, A then B taps
-__host__ __device__ constexpr int wpitch(int ta, int tb) { return ta + tb + 4; }
-__host__ __device__ constexpr int tab_bytes(int ta, int tb) { return T_BAND + 64 * wpitch(ta, tb) * 4; }
+constexpr int T_BAND = 21056;                // [64][WP] floats: lane-major band weights, A then B taps (packed form: a | b | c)
+// (pc: the third partition of the packed form, 0 otherwise; the pitch stays an odd number of 16-byte units: conflict-free b128)
+__host__ __device__ constexpr int wpitch(int ta, int tb, int pc = 0) { return ta + tb + pc + 4; }
+__host__ __device__ constexpr int tab_bytes(int ta, int tb, int pc = 0) { return T_BAND + 64 * wpitch(ta, tb, pc) * 4; }
 constexpr int DCT_PITCH = 36;                // floats per lane of the DCT operand table (9 x 16 B: conflict-free b128)
-__host__ __device__ constexpr int block_lds_bytes(int ta, int tb, bool cc) {
-    return tab_bytes(ta, tb) + (cc ? 64 * DCT_PITCH * 4 : 0) + WAVES * WAVE_LDS + CLAIM_LDS;  // (complex results: fewer waves, less)
+__host__ __device__ constexpr int block_lds_bytes(int ta, int tb, bool cc, int pc = 0) {
+    return tab_bytes(ta, tb, pc) + (cc ? 64 * DCT_PITCH * 4 : 0) + WAVES * WAVE_LDS + CLAIM_LDS;  // (complex results: fewer waves, less)
 }
 
 // Frames of a workgroup's range that one claim takes when `left` remain (guided: about left / (2 waves)): whole 16-frame cepstrum
@@ -104,7 +105,8 @@ struct KArgs2 {
     long long framesPerWg; // workgroup b owns frames [b framesPerWg, (b + 1) framesPerWg) (< 2^30); its waves claim runs of them
     int aligned;           // frame starts are 8-byte aligned -> float2 loads
     const float4 *tab;     // table blob
-    const int *meta;       // [6][64]: startA, startB, rowA, rowB, segIdx lo / hi
+    const int *meta;       // [6][64]: startA, startB, rowA, rowB, segIdx lo / hi; packed form [8][64]: base a / b / c, row a / b / c,
+                           // b continues a, c continues b (AfxBandPack)
     int specMap, postPow;
     float normValue;
     float *out;            // [totalFrames, num]
@@ -163,16 +165,19 @@ __device__ __forceinline__ float wave_sum(float v) {
 // CPLX: complex results (specMap 3: S, 4: S^2): a second row in LDS holds the imaginary parts for a second pass of the bank
 // STFT: no bank -- the frame's mapped spectrum row (|S|^2, |S|, |S|^2p) goes to memory as it stands in the LDS (afxk_stft2k: the
 //   producer of the dense-bank route's [T, F] rows and the STFT object's real results at n_fft 2048)
-template <int TA, int TB, int SHIFT, bool SPLIT, int CC, bool TEMPORAL, bool CPLX = false, bool STFT = false>
+// PC: > 0 the packed band plan (afx_bandplan.c): every lane runs ONE stream of TA | TB | PC taps that holds one, two or three whole
+//   rows -- 48 slots per lane where the (48, 16) variant runs 64; a row's multiply-adds and their order are those of the plain form
+template <int TA, int TB, int SHIFT, bool SPLIT, int CC, bool TEMPORAL, bool CPLX = false, bool STFT = false, int PC = 0>
 __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a) {
     constexpr int NWV = waves_of(CPLX);
     static_assert(!(CPLX && (CC || TEMPORAL)), "complex results: the bank only");
     static_assert(!STFT || (TA == 0 && TB == 0 && !SPLIT && CC == 0 && !TEMPORAL && !CPLX), "STFT instantiations: real rows, no bank");
+    static_assert(PC == 0 || (!SPLIT && !STFT), "packed plans hold whole rows");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    constexpr int WP = wpitch(TA, TB);
-    constexpr int TABB = tab_bytes(TA, TB);
+    constexpr int WP = wpitch(TA, TB, PC);
+    constexpr int TABB = tab_bytes(TA, TB, PC);
     constexpr int DCTB = CC == 1 ? 64 * DCT_PITCH * 4 : 0;
     unsigned char *wreg = smem + TABB + DCTB + wave * WAVE_LDS;
     float *prow = reinterpret_cast<float *>(wreg + PROW_OFF);
@@ -228,17 +233,19 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
     const unsigned aQ23 = R + 4 * (lane == 0 ? 640 : 256 - lane);      // s = 0 slots 3, 2 | lane 0: (640, 896)
     const bool lane0 = (lane == 0);
 
-    const int startA = STFT ? 0 : a.meta[lane], startB = STFT ? 0 : a.meta[64 + lane];
-    const int rowA = STFT ? -1 : a.meta[128 + lane], rowB = STFT ? -1 : a.meta[192 + lane];
+    constexpr int MROW = PC ? 192 : 128;  // the rows' numbers stand behind the starts
+    const int startA = STFT ? 0 : a.meta[lane], startB = STFT ? 0 : a.meta[64 + lane], startC = PC ? a.meta[128 + lane] : 0;
+    const int rowA = STFT ? -1 : a.meta[MROW + lane], rowB = STFT ? -1 : a.meta[MROW + 64 + lane], rowC = PC ? a.meta[MROW + 128 + lane] : -1;
     const unsigned seg0 = SPLIT ? (unsigned)a.meta[256 + lane] : 0u, seg1 = SPLIT ? (unsigned)a.meta[320 + lane] : 0u;
-    const unsigned apa = R + 4 * startA, apb = R + 4 * startB;
+    const bool contB = PC ? a.meta[384 + lane] != 0 : false, contC = PC ? a.meta[448 + lane] != 0 : false;
+    const unsigned apa = R + 4 * startA, apb = R + 4 * startB, apc = R + 4 * startC;
     const unsigned awr = T0 + T_BAND + 4 * WP * lane;
     // global memory, per lane and loop-invariant: byte offsets from wave-uniform (scalar) bases -- the frame loop forms no 64-bit
     // address on the vector unit.  vRaw: the lane's float2 in a 512-byte row of samples; vRowA / vRowB: its two bank rows' slots
     // in an output row (okA / okB: the lane has such a row); rowPitch: floats from one output row to the next
     const unsigned vRaw = 8u * (unsigned)lane, vLane = 4u * (unsigned)lane;
-    const bool okA = rowA >= 0, okB = rowB >= 0;
-    const unsigned vRowA = okA ? 4u * (unsigned)rowA : 0u, vRowB = okB ? 4u * (unsigned)rowB : 0u;
+    const bool okA = rowA >= 0, okB = rowB >= 0, okC = rowC >= 0;
+    const unsigned vRowA = okA ? 4u * (unsigned)rowA : 0u, vRowB = okB ? 4u * (unsigned)rowB : 0u, vRowC = okC ? 4u * (unsigned)rowC : 0u;
     const long long rowPitch = STFT ? a.outPitch : (long long)a.num;
 
     // ---- frame runs: no wave owns a share of the workgroup's range [wgBeg, wgBeg + wgN) -- a wave that runs out of frames claims
@@ -632,6 +639,7 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
 #pragma unroll
         for (int pass = 0; pass < (CPLX ? 2 : 1); ++pass) {
         const unsigned bpa = (CPLX && pass) ? apa - PROW_OFF : apa, bpb = (CPLX && pass) ? apb - PROW_OFF : apb;
+        const unsigned bpc = (CPLX && pass) ? apc - PROW_OFF : apc;
         if (!CPLX && a.specMap) {
             // magnitude / norm exponent (rare modes): one pass over the row in LDS.  (Applied to the 17 register values
             // before the stores, the two branches' results met the plain path's in different registers and the plain
@@ -665,8 +673,14 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
         // ---- 4. banded filter bank: weights by ds_read_b128, power row by immediate-offset
         //         ds_read_b64 (conflict-free by the plan's bank-aware lane assignment); the NEXT
         //         block of four quads is requested before this block's values are waited for --------
-        float accA, accB;
-        {
+        float accA, accB, accC = 0.f;
+        if constexpr (PC > 0) {
+            v2 sA, sB, sC;
+            band_stage3<TA, TB, PC, 4, CPLX>(awr, bpa, bpb, bpc, contB, contC, sA, sB, sC);
+            accA = sA.x + sA.y;
+            accB = sB.x + sB.y;
+            accC = sC.x + sC.y;
+        } else {
             v2 sA, sB;
             band_stage<TA, TB, 4, CPLX>(awr, bpa, bpb, sA, sB);
             accA = sA.x + sA.y;
@@ -675,6 +689,7 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
         if (!CPLX && !SPLIT && a.postPow) {
             accA = powf(accA, a.normValue);
             accB = powf(accB, a.normValue);
+            if constexpr (PC > 0) accC = powf(accC, a.normValue);
         }
         MEL_PHASE(6);
         // ---- 5. store (first the cepstra of the 16 rows stored before this one, if that many wait) ----
@@ -704,6 +719,9 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
         } else {
             if (okA) GST32_S(vRowA, accA, srow);
             if (okB) GST32_S(vRowB, accB, srow);
+            if constexpr (PC > 0) {
+                if (okC) GST32_S(vRowC, accC, srow);
+            }
         }
         if constexpr (CC != 0) {
             ++ccN;
@@ -814,7 +832,7 @@ void stamps_end(unsigned long long *d, long long blocks, int waves, void *stream
 }
 #endif
 
-template <int TA, int TB, int SHIFT, bool SPLIT, int CC, bool TEMPORAL, bool CPLX = false>
+template <int TA, int TB, int SHIFT, bool SPLIT, int CC, bool TEMPORAL, bool CPLX = false, int PC = 0>
 int launch_variant(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
     const long long total = (long long)a->batch * a->timeLength;
     if (total <= 0) return AFX_OK;
@@ -846,12 +864,12 @@ int launch_variant(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) 
     k.energy = a->energy;
     k.rms = a->rms;
     k.zcr = a->zcr;
-    constexpr size_t lds = (size_t)block_lds_bytes(TA, TB, CC == 1);
+    constexpr size_t lds = (size_t)block_lds_bytes(TA, TB, CC == 1, PC);
     static_assert(lds <= 163840, "workgroup LDS budget");
 #ifdef AFX_V2_STAMPS
     if (!(k.stamps = stamps_begin(blocks, NWV))) return AFX_ERR_HIP;
 #endif
-    AFX_LAUNCH_DYN_LDS((k_stft_mel_v2<TA, TB, SHIFT, SPLIT, CC, TEMPORAL, CPLX>), dim3((unsigned)blocks), dim3(NWV * 64), lds, stream, k);
+    AFX_LAUNCH_DYN_LDS((k_stft_mel_v2<TA, TB, SHIFT, SPLIT, CC, TEMPORAL, CPLX, false, PC>), dim3((unsigned)blocks), dim3(NWV * 64), lds, stream, k);
     AFX_LAUNCH_CHECK("k_stft_mel_v2");
 #ifdef AFX_V2_STAMPS
     stamps_end(k.stamps, blocks, NWV, stream);
@@ -859,18 +877,18 @@ int launch_variant(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) 
     return AFX_OK;
 }
 
-template <int TA, int TB, bool SPLIT, int CC, bool TEMPORAL>
+template <int TA, int TB, bool SPLIT, int CC, bool TEMPORAL, int PC = 0>
 int launch_hop(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
     // register re-use of the overlapping frames for hop = 128 * SHIFT: N/8, N/4, N/2
 #ifdef AFX_EXPERIMENTS  // measurement builds only (make EXTRA=-DAFX_EXPERIMENTS): AFX_EXP_MEL=noshift fetches every frame whole
     if (const char *e = getenv("AFX_EXP_MEL"))
-        if (strstr(e, "noshift")) return launch_variant<TA, TB, 0, SPLIT, CC, TEMPORAL>(p, a, stream);
+        if (strstr(e, "noshift")) return launch_variant<TA, TB, 0, SPLIT, CC, TEMPORAL, false, PC>(p, a, stream);
 #endif
     switch (a->hop) {
-        case 256: return launch_variant<TA, TB, 2, SPLIT, CC, TEMPORAL>(p, a, stream);
-        case 512: return launch_variant<TA, TB, 4, SPLIT, CC, TEMPORAL>(p, a, stream);
-        case 1024: return launch_variant<TA, TB, 8, SPLIT, CC, TEMPORAL>(p, a, stream);
-        default: return launch_variant<TA, TB, 0, SPLIT, CC, TEMPORAL>(p, a, stream);
+        case 256: return launch_variant<TA, TB, 2, SPLIT, CC, TEMPORAL, false, PC>(p, a, stream);
+        case 512: return launch_variant<TA, TB, 4, SPLIT, CC, TEMPORAL, false, PC>(p, a, stream);
+        case 1024: return launch_variant<TA, TB, 8, SPLIT, CC, TEMPORAL, false, PC>(p, a, stream);
+        default: return launch_variant<TA, TB, 0, SPLIT, CC, TEMPORAL, false, PC>(p, a, stream);
     }
 }
 
@@ -906,7 +924,38 @@ int launch(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
                     : launch_hop<TA, TB, false, 0, false>(p, a, stream);
 }
 
+// the routes of launch() for a packed plan (whole rows only): same checks, same choices
+template <int PA, int PB, int PC>
+int launch_packed(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
+    const bool cc = a->cc != nullptr, tmp = a->energy != nullptr;
+    if (a->specMap >= 3) {
+        if (cc || tmp) return AFX_ERR_UNSUPPORTED;
+        if (!a->outIm) return AFX_ERR_ARG;
+        if (a->hop == 512) return launch_variant<PA, PB, 4, false, 0, false, true, PC>(p, a, stream);
+        return launch_variant<PA, PB, 0, false, 0, false, true, PC>(p, a, stream);
+    }
+    if (cc && tmp) return AFX_ERR_UNSUPPORTED;
+    if (cc) {
+        if (a->ccNum < 1 || a->ccNum > 16 || !a->dct || !a->out || p->num > 128 || (p->num & 3)) return AFX_ERR_UNSUPPORTED;
+        if (a->ccRectify != 0 && a->ccRectify != 1) return AFX_ERR_UNSUPPORTED;
+        static_assert(block_lds_bytes(PA, PB, true, PC) <= 163840, "the headline form: DCT operand in LDS");
+        if (p->num == 128 && a->ccRectify == 0) return launch_hop<PA, PB, false, 1, false, PC>(p, a, stream);
+        if (a->hop == 512) return launch_variant<PA, PB, 4, false, 2, false, false, PC>(p, a, stream);
+        return launch_variant<PA, PB, 0, false, 2, false, false, PC>(p, a, stream);
+    }
+    if (tmp) {
+        if (!a->rms || !a->zcr) return AFX_ERR_ARG;
+        return launch_hop<PA, PB, false, 0, true, PC>(p, a, stream);
+    }
+    return launch_hop<PA, PB, false, 0, false, PC>(p, a, stream);
+}
+
+// the compiled layouts (a, b, c) of the packed plan: 48 slots per lane.  (24, 12, 8) and (20, 12, 12), 44 slots, hold mel-128 at
+// 16 kHz too, but the planner places them only with 5 and 3 lane pairs on one bank pair (afx_bandplan.c)
+constexpr int kPacks[][3] = {{24, 12, 12}};
+
 int run(const AfxMelPlan *p, const AfxMelFusedArgs *a, void *stream) {
+    if (p->pack == 1) return launch_packed<24, 12, 12>(p, a, stream);
     return p->variant == 0 ? launch<48, 16>(p, a, stream) : launch<72, 32>(p, a, stream);
 }
 
@@ -951,7 +1000,7 @@ int launch_stft2k(const AfxStftArgs *a, const float *tab, void *stream) {
 }  // namespace
 
 const AfxMelSize *afx_mel_size2k() {
-    static const AfxMelSize size = {11, 0, kVariants, 2, T_BAND, fill_tables, run};
+    static const AfxMelSize size = {11, 0, kVariants, 2, T_BAND, fill_tables, run, kPacks, 1, PROW_F};
     return &size;
 }
 

@@ -152,4 +152,79 @@ __device__ __forceinline__ void band_stage(unsigned awr, unsigned apa, unsigned 
     }
 }
 
+// The packed form (AfxBandPack, afx_bandpack.h): ONE stream of PA | PB | PC taps per lane, weights [PA + PB + PC (+ 4)] floats at
+// awr, three power-row addresses ap0 / ap1 / ap2.  A partition starts its sum from the one before (cont1 / cont2: it continues
+// that row; loop-invariant lane masks) or from zero; s0 / s1 / s2 are the sums at the END of each partition, so a row's
+// multiply-adds are those of band_stage, in the same order, whichever partitions it lies in: leading zero weights give
+// fma(0, p, +0) = +0, trailing ones s + 0 p = s (finite p).  Requests, waits and pins as in band_stage.
+template <int PA, int PB, int PC, int BLK, bool PINSUMS>
+__device__ __forceinline__ void band_stage3(unsigned awr, unsigned ap0, unsigned ap1, unsigned ap2, bool cont1, bool cont2, v2 &s0, v2 &s1,
+                                            v2 &s2) {
+    constexpr int Q0 = PA / 4, Q1 = Q0 + PB / 4, QT = Q1 + PC / 4, NB = (QT + BLK - 1) / BLK;
+    static_assert(BLK <= 4, "the wait ladder counts up to four quads in flight");
+    static_assert(PA % 4 == 0 && PB % 4 == 0 && PC % 4 == 0 && PA > 0 && PB > 0 && PC > 0, "partitions are whole quads");
+    s0 = v2{0.f, 0.f};
+    s1 = v2{0.f, 0.f};
+    s2 = v2{0.f, 0.f};
+    v4f w[2][BLK];
+    v2 p0[2][BLK], p1[2][BLK];
+    auto request = [&](int blk, v4f (&wq)[BLK], v2 (&q0v)[BLK], v2 (&q1v)[BLK]) {
+#pragma unroll
+        for (int i = 0; i < BLK; ++i) {
+            const int q = blk * BLK + i;
+            if (q >= QT) continue;
+            RD128_S(3, wq[i], awr, 16 * q);
+            if (q < Q0) {
+                RD64_S(3, q0v[i], ap0, 16 * q);
+                RD64_S(3, q1v[i], ap0, 16 * q + 8);
+            } else if (q < Q1) {
+                RD64_S(3, q0v[i], ap1, 16 * (q - Q0));
+                RD64_S(3, q1v[i], ap1, 16 * (q - Q0) + 8);
+            } else {
+                RD64_S(3, q0v[i], ap2, 16 * (q - Q1));
+                RD64_S(3, q1v[i], ap2, 16 * (q - Q1) + 8);
+            }
+        }
+    };
+    request(0, w[0], p0[0], p1[0]);
+#pragma unroll
+    for (int blk = 0; blk < NB; ++blk) {
+        const int cur = blk & 1;
+        const int nextQuads = (blk + 1 < NB) ? ((QT - (blk + 1) * BLK) < BLK ? (QT - (blk + 1) * BLK) : BLK) : 0;
+        if (blk + 1 < NB) request(blk + 1, w[cur ^ 1], p0[cur ^ 1], p1[cur ^ 1]);
+        if (nextQuads == 4) LDS_WAIT_N(12);
+        else if (nextQuads == 3) LDS_WAIT_N(9);
+        else if (nextQuads == 2) LDS_WAIT_N(6);
+        else if (nextQuads == 1) LDS_WAIT_N(3);
+        else LDS_WAIT_N(0);
+#pragma unroll
+        for (int i = 0; i < BLK; ++i) {
+            const int q = blk * BLK + i;
+            if (q >= QT) continue;
+            PIN(w[cur][i]);
+            PIN(p0[cur][i]);
+            PIN(p1[cur][i]);
+            if (q == Q0) s1 = cont1 ? s0 : v2{0.f, 0.f};
+            if (q == Q1) s2 = cont2 ? s1 : v2{0.f, 0.f};
+            if (KO_ON(6)) {
+                asm volatile("" ::"v"(w[cur][i]), "v"(p0[cur][i]), "v"(p1[cur][i]));
+            } else if (q < Q0) {
+                s0 += lo2(w[cur][i]) * p0[cur][i];
+                s0 += hi2(w[cur][i]) * p1[cur][i];
+            } else if (q < Q1) {
+                s1 += lo2(w[cur][i]) * p0[cur][i];
+                s1 += hi2(w[cur][i]) * p1[cur][i];
+            } else {
+                s2 += lo2(w[cur][i]) * p0[cur][i];
+                s2 += hi2(w[cur][i]) * p1[cur][i];
+            }
+        }
+        if constexpr (PINSUMS) {
+            PIN(s0);
+            PIN(s1);
+            PIN(s2);
+        }
+    }
+}
+
 #endif /* AFX_MELPARTS_H */
