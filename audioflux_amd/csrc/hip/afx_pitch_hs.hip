@@ -14,14 +14,14 @@
 //      of the object's device scratch (the host plan decides; the workgroups then stride over the frames);
 //   4. curve[j], j <= maxIndex: product / sum over k = 0 ... harmonicCount - 1 of slice[j (k + 1)] in that order, each
 //      thread striding over j -- a function of the slice alone;
-//   5. first argmax over minIndex ... maxIndex: thread-local with a strict >, then over the workgroup with the smaller
-//      index winning among equal values, so that rows of zeros or of -inf come out as minIndex (__vmax, flux_vector.c:1536);
+//   5. first argmax over minIndex ... maxIndex (afx_pitchparts.h): rows of zeros or of -inf come out as minIndex;
 //   6. fre = (index + 1) * (1.0 * samplate / M), the factor in double as the reference computes it.
 #include <hip/hip_runtime.h>
 
 #include "afx_device.h"
 #include "afx_hipcheck.h"
 #include "afx_ldsfft.h"
+#include "afx_pitchparts.h"
 
 namespace {
 
@@ -54,9 +54,8 @@ __global__ void __launch_bounds__(HsCfg<R>::NT) k_pitch_hs(AfxPitchHsArgs a, lon
     const int minIndex = a.minIndex, maxIndex = a.maxIndex, H = a.harmonicCount;
 
     for (long long row = blockIdx.x; row < rows; row += gridDim.x) {
-        const int b = (int)(row / a.timeLength);
-        const int t = (int)(row - (long long)b * a.timeLength);
-        const float *x = a.x + (long long)b * a.clipStride + (long long)t * a.hop;
+        int b, t;
+        const float *x = afx_pitch_row(a.x, row, a.timeLength, a.clipStride, a.hop, b, t);
 
         // 1. the windowed frame (neighbouring frames overlap: re-read through L2)
 #pragma unroll
@@ -96,7 +95,7 @@ __global__ void __launch_bounds__(HsCfg<R>::NT) k_pitch_hs(AfxPitchHsArgs a, lon
 
         // 3. the curve over 0 ... maxIndex in the reference's operation order, the thread's first maximum from minIndex on
         float bv = -__builtin_huge_valf();
-        int bi = 0x7fffffff;
+        int bi = AFX_PITCH_NONE;
         for (int j = tid; j <= maxIndex; j += NT) {
             float c = LOG ? 0.f : 1.f;
             for (int k = 0; k < H; ++k) {
@@ -104,38 +103,13 @@ __global__ void __launch_bounds__(HsCfg<R>::NT) k_pitch_hs(AfxPitchHsArgs a, lon
                 c = LOG ? c + v : c * v;
             }
             if (a.curve) a.curve[row * (maxIndex + 1) + j] = c;
-            if (j >= minIndex && (bi == 0x7fffffff || c > bv)) {
-                bv = c;
-                bi = j;
-            }
+            AFX_PITCH_CANDIDATE(bv, bi, c, j, minIndex)
         }
 
         // 4. over the workgroup: the larger value, the smaller index among equal ones
-#pragma unroll
-        for (int msk = 32; msk > 0; msk >>= 1) {
-            const float ov = __shfl_xor(bv, msk);
-            const int oi = __shfl_xor(bi, msk);
-            if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > bv || (ov == bv && oi < bi))) {
-                bv = ov;
-                bi = oi;
-            }
-        }
-        if (lane == 0) {
-            red[wave] = bv;
-            reinterpret_cast<int *>(red)[16 + wave] = bi;
-        }
-        __syncthreads();
+        AFX_PITCH_ARGMAX(NT, bv, bi, red, tid, lane, wave)
         if (tid == 0) {
-#pragma unroll
-            for (int w = 1; w < NT / 64; ++w) {
-                const float ov = red[w];
-                const int oi = reinterpret_cast<int *>(red)[16 + w];
-                if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > bv || (ov == bv && oi < bi))) {
-                    bv = ov;
-                    bi = oi;
-                }
-            }
-            if (bi == 0x7fffffff) bi = minIndex;  // no candidate at all (minIndex > maxIndex)
+            if (bi == AFX_PITCH_NONE) bi = minIndex;  // no candidate at all (minIndex > maxIndex)
             const long long at = (long long)b * a.outStride + t;
             if (a.fre) a.fre[at] = (float)((double)(bi + 1) * a.freStep);
             if (a.value) a.value[at] = bv;

@@ -13,8 +13,7 @@
 //      barrier;
 //   4. the inverse as a FORWARD transform read at the mirrored index: r[n] = F[(2N - n) mod 2N], r[n] = R[2n] + i R[2n + 1].
 //      Lags k <= maxIndex < 2N and taps n < N reach B[n + k], n + k < 3N: nothing wraps at 4N points;
-//   5. first argmax of R over minIndex ... maxIndex: thread-local with a strict >, then over the workgroup with the
-//      smaller index winning among equal values, so that a row of zeros comes out as minIndex;
+//   5. first argmax of R over minIndex ... maxIndex (afx_pitchparts.h): a row of zeros comes out as minIndex;
 //   6. fre = lg[index].
 #include <hip/hip_runtime.h>
 
@@ -23,6 +22,7 @@
 #include "afx_device.h"
 #include "afx_hipcheck.h"
 #include "afx_ldsfft.h"
+#include "afx_pitchparts.h"
 
 namespace {
 
@@ -57,9 +57,8 @@ __global__ void __launch_bounds__(PefCfg<R>::NT) k_pitch_pef(AfxPitchPefArgs a, 
         // against 49 / 58 with the addresses recomputed per pass
         int tid = threadIdx.x;
         PIN(tid);
-        const int b = (int)(row / a.timeLength);
-        const int t = (int)(row - (long long)b * a.timeLength);
-        const float *x = a.x + (long long)b * a.clipStride + (long long)t * a.hop;
+        int b, t;
+        const float *x = afx_pitch_row(a.x, row, a.timeLength, a.clipStride, a.hop, b, t);
 
         // 1. the windowed frame, packed and zero-padded (neighbouring frames overlap: re-read through L2)
         for (int q = tid; q < N; q += NT) {
@@ -145,44 +144,19 @@ __global__ void __launch_bounds__(PefCfg<R>::NT) k_pitch_pef(AfxPitchPefArgs a, 
 
         // 4. the lags 0 ... maxIndex, the thread's first maximum from minIndex on
         float bv = -__builtin_huge_valf();
-        int bi = 0x7fffffff;
+        int bi = AFX_PITCH_NONE;
         for (int k = tid; k <= maxIndex; k += NT) {
             const int n = (N2 - (k >> 1)) & (N2 - 1);
             const float2 r = s[afx_lds_pad((int)(__brev((unsigned)n) >> (31 - R)))];
             const float c = (k & 1) ? r.y : r.x;
             if (a.curve) a.curve[row * (maxIndex + 1) + k] = c;
-            if (k >= minIndex && (bi == 0x7fffffff || c > bv)) {
-                bv = c;
-                bi = k;
-            }
+            AFX_PITCH_CANDIDATE(bv, bi, c, k, minIndex)
         }
 
         // 5. over the workgroup: the larger value, the smaller index among equal ones
-#pragma unroll
-        for (int msk = 32; msk > 0; msk >>= 1) {
-            const float ov = __shfl_xor(bv, msk);
-            const int oi = __shfl_xor(bi, msk);
-            if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > bv || (ov == bv && oi < bi))) {
-                bv = ov;
-                bi = oi;
-            }
-        }
-        if (lane == 0) {
-            red[wave] = bv;
-            reinterpret_cast<int *>(red)[16 + wave] = bi;
-        }
-        __syncthreads();
+        AFX_PITCH_ARGMAX(NT, bv, bi, red, tid, lane, wave)
         if (tid == 0) {
-#pragma unroll
-            for (int w = 1; w < NT / 64; ++w) {
-                const float ov = red[w];
-                const int oi = reinterpret_cast<int *>(red)[16 + w];
-                if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > bv || (ov == bv && oi < bi))) {
-                    bv = ov;
-                    bi = oi;
-                }
-            }
-            if (bi == 0x7fffffff) bi = minIndex;  // every candidate a NaN
+            if (bi == AFX_PITCH_NONE) bi = minIndex;  // every candidate a NaN
             const long long at = (long long)b * a.outStride + t;
             if (a.fre) a.fre[at] = a.lg[bi];
             if (a.value) a.value[at] = bv;

@@ -20,6 +20,7 @@
 #include "afx_device.h"
 #include "afx_hipcheck.h"
 #include "afx_ldsfft.h"
+#include "afx_pitchparts.h"
 
 namespace {
 
@@ -108,9 +109,8 @@ __global__ void __launch_bounds__(YinCfg<R>::NT) k_pitch_yin(AfxPitchYinArgs a) 
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long row = blockIdx.x;
-    const int b = (int)(row / a.timeLength);
-    const int t = (int)(row - (long long)b * a.timeLength);
-    const float *x = a.x + (long long)b * a.clipStride + (long long)t * a.hop;
+    int b, t;
+    const float *x = afx_pitch_row(a.x, row, a.timeLength, a.clipStride, a.hop, b, t);
     const int A = a.autoLength, minIndex = a.minIndex, maxIndex = a.maxIndex, Y = maxIndex - minIndex + 1;
 
     // 1. the frame (neighbouring frames overlap: re-read through L2)

@@ -6,6 +6,7 @@
 
 #include "afx_frametail.h"
 #include "afx_objkit.h"
+#include "afx_pitchkit.h"
 #include "flux_base.h"
 #include "reassign_algorithm.h"
 
@@ -139,65 +140,48 @@ struct OpaqueHPSS {
     int status;
 };
 
-/* the YIN pitch tracker (afx_pitch_yin.c, mir/_pitch_yin.h) */
+/* The pitch trackers: `head` (afx_pitchkit.h) holds the sizes, the tail, the stream, the staging buffers and the status. */
+
+/* YIN (afx_pitch_yin.c, mir/_pitch_yin.h); head.dOut holds [3][T] */
 struct OpaquePitchYIN {
-    int radix2Exp, fftLength, slideLength, autoLength;
+    AfxPitchHead head;
+    int autoLength;
     int minIndex, maxIndex, diffLength, yinLength; /* lags of the curve: minIndex ... maxIndex < diffLength = fftLength - autoLength */
-    int samplate;
     float thresh;
-    int isDebug;
-    AfxFrameTail tail;       /* isContinue and the samples carried between host-pointer calls */
-    int timeLength;          /* frames of the last pitchYINObj_pitch call */
-    void *stream;
     float *dTwiddle;
-    float *dX, *dOut, *dCand; /* grow-only device buffers of the host-pointer call: samples, [3][T], [2][T, mLen] + lengths */
-    size_t capX, capOut, capCand;
+    float *dCand;            /* grow-only, of the host-pointer call: [2][T, mLen] + lengths */
+    size_t capCand;
     float *hOut;             /* host staging [3][T] */
     float *mFreArr, *mTroughArr; /* host [T, mLen]: pitchYINObj_getTroughData */
     int *lenArr;
     size_t capHost;          /* frames the host arrays hold */
-    int status;
 };
 
-/* the harmonic-product-spectrum and log-harmonic-sum pitch trackers (afx_pitch_hs.c, mir/_pitch_hps.h, mir/_pitch_lhs.h):
- * one layout, `kind` selects the combining operator */
+/* harmonic product spectrum and log-harmonic sum (afx_pitch_hs.c, mir/_pitch_hps.h, mir/_pitch_lhs.h): one layout, `kind`
+ * selects the combining operator */
 struct OpaquePitchHS {
+    AfxPitchHead head;
     int kind;                /* AFX_PITCH_HPS / AFX_PITCH_LHS */
-    int radix2Exp, fftLength, slideLength;
-    int samplate, interpLength, interpExp; /* M = 2^interpExp: the zero-padded transform the reference runs per frame */
+    int interpLength, interpExp; /* M = 2^interpExp: the zero-padded transform the reference runs per frame */
     int minIndex, maxIndex, harmonicCount;
     int lastBin;             /* maxIndex * harmonicCount: the highest bin of the M-point spectrum a curve reads */
     int sliceInLds;          /* the spectrum slice fits in LDS beside the transform buffer and the frame */
     int transforms;          /* fftLength-point transforms per frame */
     WindowType windowType;
-    int isDebug;
-    AfxFrameTail tail;       /* isContinue and the samples carried between host-pointer calls */
-    int timeLength;          /* frames of the last pitch call */
-    void *stream;
     float *dWindow, *dTwiddle, *dRoots;
     float *dSlice;           /* grow-only: [groups][slice floats] of the plans whose slice does not fit in LDS */
     size_t capSlice;
-    float *dX, *dOut;        /* grow-only device buffers of the host-pointer call: samples, [T] */
-    size_t capX, capOut;
     AfxScratchStream scratchStream;
-    int status;
 };
 
-/* the pitch-estimation-filter tracker (afx_pitch_pef.c, mir/_pitch_pef.h) */
+/* the pitch-estimation filter (afx_pitch_pef.c, mir/_pitch_pef.h) */
 struct OpaquePitchPEF {
-    int radix2Exp, fftLength, slideLength, samplate;
+    AfxPitchHead head;
     int minIndex, maxIndex, filterPadNum;
     int pwLength;            /* bins of the power spectrum the log grid reads */
     float lowFre, highFre, cutFre, alpha, beta, gamma;
     WindowType windowType;
-    int isDebug;
-    AfxFrameTail tail;       /* isContinue and the samples carried between host-pointer calls */
-    int timeLength;          /* frames of the last pitch call */
-    void *stream;
     float *dWindow, *dTwiddle, *dTaps, *dFilterSpec, *dLg; /* uploaded once: [N], [4N], [2N] taps, [2N + 1] float2, [2N] */
-    float *dX, *dOut;        /* grow-only device buffers of the host-pointer call: samples, [T] */
-    size_t capX, capOut;
-    int status;
 };
 
 /* the onset detector (afx_onset.c, mir/onset_algorithm.h) */

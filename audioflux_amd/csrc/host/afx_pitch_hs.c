@@ -103,16 +103,13 @@ int afx_pitch_hs_plan_host(int kind, int *samplate, float *lowFre, float *highFr
 
 static void hs_free(struct OpaquePitchHS *o) {
     if (!o) return;
-    if (o->stream) afxdev_stream_sync(o->stream);
+    afx_pitch_head_sync(&o->head);
     afx_scratch_drain(&o->scratchStream);
     afxdev_free(o->dWindow);
     afxdev_free(o->dTwiddle);
     afxdev_free(o->dRoots);
     afxdev_free(o->dSlice);
-    afxdev_free(o->dX);
-    afxdev_free(o->dOut);
-    if (o->stream) afxdev_stream_destroy(o->stream);
-    afx_frametail_free(&o->tail);
+    afx_pitch_head_release(&o->head);
     free(o);
 }
 
@@ -129,10 +126,6 @@ static int hs_new(int kind, struct OpaquePitchHS **out, const int *samplate, con
     struct OpaquePitchHS *o = (struct OpaquePitchHS *)calloc(1, sizeof(*o));
     if (!o) return AFX_ERR_NOMEM;
     o->kind = kind;
-    o->radix2Exp = p.radix2Exp;
-    o->fftLength = p.fftLength;
-    o->slideLength = p.slideLength;
-    o->samplate = p.samplate;
     o->interpLength = p.interpLength;
     o->interpExp = afx_log2_exact(p.interpLength);
     o->minIndex = p.minIndex;
@@ -142,8 +135,7 @@ static int hs_new(int kind, struct OpaquePitchHS **out, const int *samplate, con
     o->sliceInLds = p.sliceInLds;
     o->transforms = p.transforms;
     o->windowType = (WindowType)p.windowType;
-    st = afx_frametail_init(&o->tail, p.fftLength, p.slideLength, p.isContinue);
-    if (st == AFX_OK) st = afxdev_stream_create(&o->stream);
+    st = afx_pitch_head_init(&o->head, p.radix2Exp, p.slideLength, p.samplate, p.isContinue);
     const size_t M = (size_t)p.interpLength, N = (size_t)p.fftLength;
     float *win = NULL, *tw = NULL, *roots = NULL;
     if (st == AFX_OK) {
@@ -160,13 +152,10 @@ static int hs_new(int kind, struct OpaquePitchHS **out, const int *samplate, con
             roots[2 * m + 1] = (float)-sin(ph);
         }
     }
-    if (st == AFX_OK) st = afxdev_malloc((void **)&o->dWindow, sizeof(float) * N);
-    if (st == AFX_OK) st = afxdev_malloc((void **)&o->dTwiddle, sizeof(float) * N);
-    if (st == AFX_OK) st = afxdev_malloc((void **)&o->dRoots, sizeof(float) * 2 * M);
-    if (st == AFX_OK) st = afxdev_h2d(o->dWindow, win, sizeof(float) * N, o->stream);
-    if (st == AFX_OK) st = afxdev_h2d(o->dTwiddle, tw, sizeof(float) * N, o->stream);
-    if (st == AFX_OK) st = afxdev_h2d(o->dRoots, roots, sizeof(float) * 2 * M, o->stream);
-    if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
+    st = afx_pitch_table(st, &o->dWindow, win, sizeof(float) * N, o->head.stream);
+    st = afx_pitch_table(st, &o->dTwiddle, tw, sizeof(float) * N, o->head.stream);
+    st = afx_pitch_table(st, &o->dRoots, roots, sizeof(float) * 2 * M, o->head.stream);
+    if (st == AFX_OK) st = afxdev_stream_sync(o->head.stream);
     free(win);
     free(tw);
     free(roots);
@@ -179,8 +168,9 @@ static int hs_new(int kind, struct OpaquePitchHS **out, const int *samplate, con
 }
 
 /* one launch over `batch` clips: the slice scratch of the plans that need it is reserved here */
-static int hs_run(struct OpaquePitchHS *o, const float *dData, int batch, int dataLength, long long clipStride, int T, float *dFre,
-                  float *dValue, long long outStride, float *dCurve, void *stream) {
+static int hs_run(void *ctx, const float *dData, int batch, int dataLength, long long clipStride, int T, float *dFre, float *dValue,
+                  long long outStride, float *dCurve, void *stream) {
+    struct OpaquePitchHS *o = (struct OpaquePitchHS *)ctx;
     AfxPitchHsArgs a;
     memset(&a, 0, sizeof(a));
     a.x = dData;
@@ -189,13 +179,13 @@ static int hs_run(struct OpaquePitchHS *o, const float *dData, int batch, int da
     a.dataLength = dataLength;
     a.timeLength = T;
     a.kind = o->kind;
-    a.radix2Exp = o->radix2Exp;
-    a.hop = o->slideLength;
+    a.radix2Exp = o->head.radix2Exp;
+    a.hop = o->head.slideLength;
     a.interpExp = o->interpExp;
     a.minIndex = o->minIndex;
     a.maxIndex = o->maxIndex;
     a.harmonicCount = o->harmonicCount;
-    a.freStep = 1.0 * o->samplate / o->interpLength;
+    a.freStep = 1.0 * o->head.samplate / o->interpLength;
     a.window = o->dWindow;
     a.twiddle = o->dTwiddle;
     a.roots = o->dRoots;
@@ -216,80 +206,31 @@ static int hs_run(struct OpaquePitchHS *o, const float *dData, int batch, int da
     return afxk_pitch_hs(&a, stream);
 }
 
-/* what the batched calls share: 1 = run, 0 = nothing to do, < 0 = refusal */
-static int batch_enter(struct OpaquePitchHS *o, const float *dData, int batch, int dataLength, long long clipStride, const void *out,
-                       void *hipStream, int *T) {
-    if (!o || !dData || !out || batch <= 0 || dataLength <= 0 || clipStride < dataLength) return AFX_ERR_ARG;
-    if (o->tail.isContinue) {
-        afxdev_set_error("pitch%sObj: a batched call on an object that carries one signal's tail (isContinue = 1)",
-                         o->kind == AFX_PITCH_LHS ? "LHS" : "HPS");
-        return AFX_ERR_UNSUPPORTED;
-    }
-    int st = afxdev_bind_stream(hipStream);
-    if (st != AFX_OK) return st;
-    *T = afx_frames(dataLength, o->fftLength, o->slideLength);
-    return *T > 0;
-}
-
-static int hs_pitch_batch(struct OpaquePitchHS *o, const float *dData, int batch, int dataLength, long long clipStride, float *dFre,
-                          float *dValue, long long outStride, void *hipStream) {
+static int hs_pitch_batch(struct OpaquePitchHS *o, const char *name, const float *dData, int batch, int dataLength, long long clipStride,
+                          float *dFre, float *dValue, long long outStride, void *hipStream) {
     int T = 0;
-    const int go = batch_enter(o, dData, batch, dataLength, clipStride, dFre, hipStream, &T);
+    const int go = afx_pitch_batch_enter(AFX_PITCH_HEAD(o), name, dData, batch, dataLength, clipStride, dFre, hipStream, &T);
     if (go <= 0) return go;
     if (outStride < T) return AFX_ERR_ARG;
     return hs_run(o, dData, batch, dataLength, clipStride, T, dFre, dValue, outStride, NULL, hipStream);
 }
 
-static int hs_curve_batch(struct OpaquePitchHS *o, const float *dData, int batch, int dataLength, long long clipStride, float *dCurve,
-                          void *hipStream) {
+static int hs_curve_batch(struct OpaquePitchHS *o, const char *name, const float *dData, int batch, int dataLength, long long clipStride,
+                          float *dCurve, void *hipStream) {
     int T = 0;
-    const int go = batch_enter(o, dData, batch, dataLength, clipStride, dCurve, hipStream, &T);
+    const int go = afx_pitch_batch_enter(AFX_PITCH_HEAD(o), name, dData, batch, dataLength, clipStride, dCurve, hipStream, &T);
     if (go <= 0) return go;
     return hs_run(o, dData, batch, dataLength, clipStride, T, NULL, NULL, 0, dCurve, hipStream);
 }
 
-static void hs_pitch(struct OpaquePitchHS *o, const float *dataArr, int dataLength, float *freArr, const char *who) {
-    AFX_ENTER(o);
-    if (!o) {
-        afxdev_set_error("%s: NULL object", who);
-        afxdev_report_failure(who, AFX_ERR_ARG);
-        return;
-    }
-    if (!dataArr || dataLength <= 0) return; /* _pitch_hps.c:397-399 */
-    AfxFrameTake t;
-    const int T = afx_frametail_take(&o->tail, dataLength, &t);
-    o->timeLength = T > 0 ? T : 0;
-    if (T < 0) {
-        AFX_FAIL(o, T, who);
-        return;
-    }
-    if (T == 0) {
-        afx_frametail_keep(&o->tail, dataArr, dataLength);
-        return;
-    }
-    const int n = t.total;
-    const size_t rowB = sizeof(float) * (size_t)T;
-    int st = freArr ? AFX_OK : AFX_ERR_ARG;
-    if (st == AFX_OK) st = afx_frametail_upload(&o->tail, &t, dataArr, &o->dX, &o->capX, o->stream);
-    if (st == AFX_OK) st = afxdev_reserve((void **)&o->dOut, &o->capOut, rowB);
-    if (st == AFX_OK) st = hs_run(o, o->dX, 1, n, n, T, o->dOut, NULL, T, NULL, o->stream);
-    if (st == AFX_OK) st = afxdev_d2h(freArr, o->dOut, rowB, o->stream);
-    if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
-    afx_frametail_keep(&o->tail, dataArr, dataLength); /* the samples are taken in whatever becomes of the frames */
-    if (st != AFX_OK) {
-        o->timeLength = 0;
-        AFX_FAIL(o, st, who);
-    }
-}
-
 static void hs_debug(struct OpaquePitchHS *o, int isDebug) {
     if (!o) return;
-    o->isDebug = isDebug;
+    o->head.isDebug = isDebug;
     if (isDebug)
         printf("pitch%s params is: samplate=%d, fftLength=%d, slideLength=%d, interpFFTLength=%d, minIndex=%d, maxIndex=%d, "
                "harmonicCount=%d, windowType=%d\n",
-               o->kind == AFX_PITCH_LHS ? "LHS" : "HPS", o->samplate, o->fftLength, o->slideLength, o->interpLength, o->minIndex,
-               o->maxIndex, o->harmonicCount, (int)o->windowType);
+               o->kind == AFX_PITCH_LHS ? "LHS" : "HPS", o->head.samplate, o->head.fftLength, o->head.slideLength, o->interpLength,
+               o->minIndex, o->maxIndex, o->harmonicCount, (int)o->windowType);
 }
 
 /* ---- the exported names ------------------------------------------------------------------------------------------------ */
@@ -298,19 +239,19 @@ static void hs_debug(struct OpaquePitchHS *o, int isDebug) {
                              WindowType *windowType, int *harmonicCount, int *isContinue) {                                       \
         return hs_new(KIND, obj, samplate, lowFre, highFre, radix2Exp, slideLength, windowType, harmonicCount, isContinue);       \
     }                                                                                                                             \
-    int pitch##NAME##Obj_calTimeLength(TYPE o, int dataLength) { return o ? afx_frametail_frames(&o->tail, dataLength) : 0; }     \
+    int pitch##NAME##Obj_calTimeLength(TYPE o, int dataLength) { return afx_pitch_frames(AFX_PITCH_HEAD(o), dataLength); }        \
     void pitch##NAME##Obj_pitch(TYPE o, float *dataArr, int dataLength, float *freArr) {                                          \
-        hs_pitch(o, dataArr, dataLength, freArr, "pitch" #NAME "Obj_pitch");                                                      \
+        afx_pitch_call(AFX_PITCH_HEAD(o), dataArr, dataLength, freArr, hs_run, o, "pitch" #NAME "Obj_pitch");                     \
     }                                                                                                                             \
     void pitch##NAME##Obj_enableDebug(TYPE o, int isDebug) { hs_debug(o, isDebug); }                                              \
     void pitch##NAME##Obj_free(TYPE o) { hs_free(o); }                                                                            \
     int pitch##NAME##Obj_pitchBatchDevice(TYPE o, const float *dData, int batch, int dataLength, long long clipStride,            \
                                           float *dFre, float *dValue, long long outStride, void *hipStream) {                     \
-        return hs_pitch_batch(o, dData, batch, dataLength, clipStride, dFre, dValue, outStride, hipStream);                       \
+        return hs_pitch_batch(o, "pitch" #NAME "Obj", dData, batch, dataLength, clipStride, dFre, dValue, outStride, hipStream);  \
     }                                                                                                                             \
     int pitch##NAME##Obj_curveBatchDevice(TYPE o, const float *dData, int batch, int dataLength, long long clipStride,            \
                                           float *dCurve, void *hipStream) {                                                       \
-        return hs_curve_batch(o, dData, batch, dataLength, clipStride, dCurve, hipStream);                                        \
+        return hs_curve_batch(o, "pitch" #NAME "Obj", dData, batch, dataLength, clipStride, dCurve, hipStream);                   \
     }                                                                                                                             \
     int pitch##NAME##Obj_minIndex(TYPE o) { return o ? o->minIndex : 0; }                                                         \
     int pitch##NAME##Obj_maxIndex(TYPE o) { return o ? o->maxIndex : 0; }                                                         \

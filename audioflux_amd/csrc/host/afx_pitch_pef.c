@@ -233,16 +233,13 @@ static float *pef_filter_spec(const AfxPitchPefPlan *p) {
 
 static void pef_free(struct OpaquePitchPEF *o) {
     if (!o) return;
-    if (o->stream) afxdev_stream_sync(o->stream);
+    afx_pitch_head_sync(&o->head);
     afxdev_free(o->dWindow);
     afxdev_free(o->dTwiddle);
     afxdev_free(o->dTaps);
     afxdev_free(o->dFilterSpec);
     afxdev_free(o->dLg);
-    afxdev_free(o->dX);
-    afxdev_free(o->dOut);
-    if (o->stream) afxdev_stream_destroy(o->stream);
-    afx_frametail_free(&o->tail);
+    afx_pitch_head_release(&o->head);
     free(o);
 }
 
@@ -262,10 +259,6 @@ int pitchPEFObj_new(PitchPEFObj *pitchPEFObj, int *samplate, float *lowFre, floa
         afx_pitch_pef_plan_free(&p);
         return AFX_ERR_NOMEM;
     }
-    o->radix2Exp = p.radix2Exp;
-    o->fftLength = p.fftLength;
-    o->slideLength = p.slideLength;
-    o->samplate = p.samplate;
     o->minIndex = p.minIndex;
     o->maxIndex = p.maxIndex;
     o->filterPadNum = p.filterPadNum;
@@ -277,8 +270,7 @@ int pitchPEFObj_new(PitchPEFObj *pitchPEFObj, int *samplate, float *lowFre, floa
     o->beta = p.beta;
     o->gamma = p.gamma;
     o->windowType = (WindowType)p.windowType;
-    st = afx_frametail_init(&o->tail, p.fftLength, p.slideLength, p.isContinue);
-    if (st == AFX_OK) st = afxdev_stream_create(&o->stream);
+    st = afx_pitch_head_init(&o->head, p.radix2Exp, p.slideLength, p.samplate, p.isContinue);
     const size_t N = (size_t)p.fftLength;
     float *tw = NULL, *spec = NULL;
     AfxPitchPefTap *taps = NULL;
@@ -289,17 +281,12 @@ int pitchPEFObj_new(PitchPEFObj *pitchPEFObj, int *samplate, float *lowFre, floa
         if (!tw || !taps || !spec) st = AFX_ERR_NOMEM;
     }
     const size_t specB = sizeof(float) * 2 * (2 * N + 1);
-    if (st == AFX_OK) st = afxdev_malloc((void **)&o->dWindow, sizeof(float) * N);
-    if (st == AFX_OK) st = afxdev_malloc((void **)&o->dTwiddle, sizeof(float) * 4 * N);
-    if (st == AFX_OK) st = afxdev_malloc((void **)&o->dTaps, sizeof(*taps) * 2 * N);
-    if (st == AFX_OK) st = afxdev_malloc((void **)&o->dFilterSpec, specB);
-    if (st == AFX_OK) st = afxdev_malloc((void **)&o->dLg, sizeof(float) * 2 * N);
-    if (st == AFX_OK) st = afxdev_h2d(o->dWindow, p.window, sizeof(float) * N, o->stream);
-    if (st == AFX_OK) st = afxdev_h2d(o->dTwiddle, tw, sizeof(float) * 4 * N, o->stream);
-    if (st == AFX_OK) st = afxdev_h2d(o->dTaps, taps, sizeof(*taps) * 2 * N, o->stream);
-    if (st == AFX_OK) st = afxdev_h2d(o->dFilterSpec, spec, specB, o->stream);
-    if (st == AFX_OK) st = afxdev_h2d(o->dLg, p.lg, sizeof(float) * 2 * N, o->stream);
-    if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
+    st = afx_pitch_table(st, &o->dWindow, p.window, sizeof(float) * N, o->head.stream);
+    st = afx_pitch_table(st, &o->dTwiddle, tw, sizeof(float) * 4 * N, o->head.stream);
+    st = afx_pitch_table(st, &o->dTaps, taps, sizeof(*taps) * 2 * N, o->head.stream);
+    st = afx_pitch_table(st, &o->dFilterSpec, spec, specB, o->head.stream);
+    st = afx_pitch_table(st, &o->dLg, p.lg, sizeof(float) * 2 * N, o->head.stream);
+    if (st == AFX_OK) st = afxdev_stream_sync(o->head.stream);
     free(tw);
     free(taps);
     free(spec);
@@ -313,8 +300,9 @@ int pitchPEFObj_new(PitchPEFObj *pitchPEFObj, int *samplate, float *lowFre, floa
 }
 
 /* one launch over `batch` clips */
-static int pef_run(struct OpaquePitchPEF *o, const float *dData, int batch, int dataLength, long long clipStride, int T,
-                   float *dFre, float *dValue, long long outStride, float *dCurve, void *stream) {
+static int pef_run(void *ctx, const float *dData, int batch, int dataLength, long long clipStride, int T, float *dFre, float *dValue,
+                   long long outStride, float *dCurve, void *stream) {
+    const struct OpaquePitchPEF *o = (const struct OpaquePitchPEF *)ctx;
     AfxPitchPefArgs a;
     memset(&a, 0, sizeof(a));
     a.x = dData;
@@ -322,8 +310,8 @@ static int pef_run(struct OpaquePitchPEF *o, const float *dData, int batch, int 
     a.batch = batch;
     a.dataLength = dataLength;
     a.timeLength = T;
-    a.radix2Exp = o->radix2Exp;
-    a.hop = o->slideLength;
+    a.radix2Exp = o->head.radix2Exp;
+    a.hop = o->head.slideLength;
     a.minIndex = o->minIndex;
     a.maxIndex = o->maxIndex;
     a.filterPadNum = o->filterPadNum;
@@ -340,24 +328,10 @@ static int pef_run(struct OpaquePitchPEF *o, const float *dData, int batch, int 
     return afxk_pitch_pef(&a, stream);
 }
 
-/* what the batched calls share: 1 = run, 0 = nothing to do, < 0 = refusal */
-static int batch_enter(struct OpaquePitchPEF *o, const float *dData, int batch, int dataLength, long long clipStride,
-                       const void *out, void *hipStream, int *T) {
-    if (!o || !dData || !out || batch <= 0 || dataLength <= 0 || clipStride < dataLength) return AFX_ERR_ARG;
-    if (o->tail.isContinue) {
-        afxdev_set_error("pitchPEFObj: a batched call on an object that carries one signal's tail (isContinue = 1)");
-        return AFX_ERR_UNSUPPORTED;
-    }
-    int st = afxdev_bind_stream(hipStream);
-    if (st != AFX_OK) return st;
-    *T = afx_frames(dataLength, o->fftLength, o->slideLength);
-    return *T > 0;
-}
-
 int pitchPEFObj_pitchBatchDevice(PitchPEFObj o, const float *dData, int batch, int dataLength, long long clipStride, float *dFre,
                                  float *dValue, long long outStride, void *hipStream) {
     int T = 0;
-    const int go = batch_enter(o, dData, batch, dataLength, clipStride, dFre, hipStream, &T);
+    const int go = afx_pitch_batch_enter(AFX_PITCH_HEAD(o), "pitchPEFObj", dData, batch, dataLength, clipStride, dFre, hipStream, &T);
     if (go <= 0) return go;
     if (outStride < T) return AFX_ERR_ARG;
     return pef_run(o, dData, batch, dataLength, clipStride, T, dFre, dValue, outStride, NULL, hipStream);
@@ -366,47 +340,16 @@ int pitchPEFObj_pitchBatchDevice(PitchPEFObj o, const float *dData, int batch, i
 int pitchPEFObj_curveBatchDevice(PitchPEFObj o, const float *dData, int batch, int dataLength, long long clipStride,
                                  float *dCurve, void *hipStream) {
     int T = 0;
-    const int go = batch_enter(o, dData, batch, dataLength, clipStride, dCurve, hipStream, &T);
+    const int go = afx_pitch_batch_enter(AFX_PITCH_HEAD(o), "pitchPEFObj", dData, batch, dataLength, clipStride, dCurve, hipStream, &T);
     if (go <= 0) return go;
     return pef_run(o, dData, batch, dataLength, clipStride, T, NULL, NULL, 0, dCurve, hipStream);
 }
 
 void pitchPEFObj_pitch(PitchPEFObj o, float *dataArr, int dataLength, float *freArr) {
-    static const char *who = "pitchPEFObj_pitch";
-    AFX_ENTER(o);
-    if (!o) {
-        afxdev_set_error("%s: NULL object", who);
-        afxdev_report_failure(who, AFX_ERR_ARG);
-        return;
-    }
-    if (!dataArr || dataLength <= 0) return; /* _pitch_pef.c:237-239 */
-    AfxFrameTake t;
-    const int T = afx_frametail_take(&o->tail, dataLength, &t);
-    o->timeLength = T > 0 ? T : 0;
-    if (T < 0) {
-        AFX_FAIL(o, T, who);
-        return;
-    }
-    if (T == 0) {
-        afx_frametail_keep(&o->tail, dataArr, dataLength);
-        return;
-    }
-    const int n = t.total;
-    const size_t rowB = sizeof(float) * (size_t)T;
-    int st = freArr ? AFX_OK : AFX_ERR_ARG;
-    if (st == AFX_OK) st = afx_frametail_upload(&o->tail, &t, dataArr, &o->dX, &o->capX, o->stream);
-    if (st == AFX_OK) st = afxdev_reserve((void **)&o->dOut, &o->capOut, rowB);
-    if (st == AFX_OK) st = pef_run(o, o->dX, 1, n, n, T, o->dOut, NULL, T, NULL, o->stream);
-    if (st == AFX_OK) st = afxdev_d2h(freArr, o->dOut, rowB, o->stream);
-    if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
-    afx_frametail_keep(&o->tail, dataArr, dataLength); /* the samples are taken in whatever becomes of the frames */
-    if (st != AFX_OK) {
-        o->timeLength = 0;
-        AFX_FAIL(o, st, who);
-    }
+    afx_pitch_call(AFX_PITCH_HEAD(o), dataArr, dataLength, freArr, pef_run, o, "pitchPEFObj_pitch");
 }
 
-int pitchPEFObj_calTimeLength(PitchPEFObj o, int dataLength) { return o ? afx_frametail_frames(&o->tail, dataLength) : 0; }
+int pitchPEFObj_calTimeLength(PitchPEFObj o, int dataLength) { return afx_pitch_frames(AFX_PITCH_HEAD(o), dataLength); }
 
 /* _pitch_pef.c:685-694: the reference validates, then rebuilds the filter from the values it STORED at construction: no
  * observable change, so none here */
@@ -416,11 +359,11 @@ void pitchPEFObj_setFilterParams(PitchPEFObj o, float alpha, float beta, float g
 
 void pitchPEFObj_enableDebug(PitchPEFObj o, int isDebug) {
     if (!o) return;
-    o->isDebug = isDebug;
+    o->head.isDebug = isDebug;
     if (isDebug)
         printf("pitchPEF params is: samplate=%d, fftLength=%d, slideLength=%d, lowFre=%g, highFre=%g, cutFre=%g, minIndex=%d, "
                "maxIndex=%d, alpha=%g, beta=%g, gamma=%g, filterPadNum=%d, windowType=%d\n",
-               o->samplate, o->fftLength, o->slideLength, o->lowFre, o->highFre, o->cutFre, o->minIndex, o->maxIndex, o->alpha,
+               o->head.samplate, o->head.fftLength, o->head.slideLength, o->lowFre, o->highFre, o->cutFre, o->minIndex, o->maxIndex, o->alpha,
                o->beta, o->gamma, o->filterPadNum, (int)o->windowType);
 }
 
@@ -428,4 +371,4 @@ void pitchPEFObj_free(PitchPEFObj o) { pef_free(o); }
 int pitchPEFObj_minIndex(PitchPEFObj o) { return o ? o->minIndex : 0; }
 int pitchPEFObj_maxIndex(PitchPEFObj o) { return o ? o->maxIndex : 0; }
 int pitchPEFObj_filterPadNum(PitchPEFObj o) { return o ? o->filterPadNum : 0; }
-int pitchPEFObj_logLength(PitchPEFObj o) { return o ? 2 * o->fftLength : 0; }
+int pitchPEFObj_logLength(PitchPEFObj o) { return o ? 2 * o->head.fftLength : 0; }

@@ -83,27 +83,20 @@ int pitchYINObj_new(PitchYINObj *pitchYINObj, int *samplate, float *lowFre, floa
     if (st != AFX_OK) return st;
     PitchYINObj o = (PitchYINObj)calloc(1, sizeof(struct OpaquePitchYIN));
     if (!o) return AFX_ERR_NOMEM;
-    o->radix2Exp = p.radix2Exp;
-    o->fftLength = p.fftLength;
-    o->slideLength = p.slideLength;
     o->autoLength = p.autoLength;
     o->minIndex = p.minIndex;
     o->maxIndex = p.maxIndex;
     o->diffLength = p.diffLength;
     o->yinLength = p.yinLength;
-    o->samplate = p.samplate;
     o->thresh = 0.1f;
-    st = afx_frametail_init(&o->tail, p.fftLength, p.slideLength, p.isContinue);
-    if (st == AFX_OK) st = afxdev_stream_create(&o->stream);
+    st = afx_pitch_head_init(&o->head, p.radix2Exp, p.slideLength, p.samplate, p.isContinue);
     float *tw = NULL;
-    const size_t twB = sizeof(float) * (size_t)p.fftLength;
     if (st == AFX_OK) {
         tw = afx_twiddle_table(p.fftLength);
         if (!tw) st = AFX_ERR_NOMEM;
     }
-    if (st == AFX_OK) st = afxdev_malloc((void **)&o->dTwiddle, twB);
-    if (st == AFX_OK) st = afxdev_h2d(o->dTwiddle, tw, twB, o->stream);
-    if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
+    st = afx_pitch_table(st, &o->dTwiddle, tw, sizeof(float) * (size_t)p.fftLength, o->head.stream);
+    if (st == AFX_OK) st = afxdev_stream_sync(o->head.stream);
     free(tw);
     if (st != AFX_OK) {
         pitchYINObj_free(o);
@@ -117,10 +110,7 @@ void pitchYINObj_setThresh(PitchYINObj o, float thresh) {
     if (o && thresh > 0) o->thresh = thresh;
 }
 
-int pitchYINObj_calTimeLength(PitchYINObj o, int dataLength) {
-    if (!o) return 0;
-    return afx_frametail_frames(&o->tail, dataLength);
-}
+int pitchYINObj_calTimeLength(PitchYINObj o, int dataLength) { return afx_pitch_frames(AFX_PITCH_HEAD(o), dataLength); }
 
 int pitchYINObj_yinLength(PitchYINObj o) { return o ? o->yinLength : 0; }
 int pitchYINObj_minIndex(PitchYINObj o) { return o ? o->minIndex : 0; }
@@ -133,34 +123,20 @@ static void fill_args(const struct OpaquePitchYIN *o, const float *dData, int ba
     a->batch = batch;
     a->dataLength = dataLength;
     a->timeLength = T;
-    a->radix2Exp = o->radix2Exp;
-    a->hop = o->slideLength;
+    a->radix2Exp = o->head.radix2Exp;
+    a->hop = o->head.slideLength;
     a->autoLength = o->autoLength;
     a->minIndex = o->minIndex;
     a->maxIndex = o->maxIndex;
-    a->samplate = o->samplate;
+    a->samplate = o->head.samplate;
     a->thresh = o->thresh;
     a->twiddle = o->dTwiddle;
-}
-
-/* what the three batched calls share: 1 = run, 0 = nothing to do, < 0 = refusal */
-static int batch_enter(PitchYINObj o, const float *dData, int batch, int dataLength, long long clipStride, const void *out,
-                       void *hipStream, int *T) {
-    if (!o || !dData || !out || batch <= 0 || dataLength <= 0 || clipStride < dataLength) return AFX_ERR_ARG;
-    if (o->tail.isContinue) {
-        afxdev_set_error("pitchYINObj: a batched call on an object that carries one signal's tail (isContinue = 1)");
-        return AFX_ERR_UNSUPPORTED;
-    }
-    int st = afxdev_bind_stream(hipStream);
-    if (st != AFX_OK) return st;
-    *T = afx_frames(dataLength, o->fftLength, o->slideLength);
-    return *T > 0;
 }
 
 int pitchYINObj_pitchBatchDevice(PitchYINObj o, const float *dData, int batch, int dataLength, long long clipStride, float *dFre,
                                  float *dTrough, float *dMin, long long outStride, void *hipStream) {
     int T = 0;
-    const int go = batch_enter(o, dData, batch, dataLength, clipStride, dFre, hipStream, &T);
+    const int go = afx_pitch_batch_enter(AFX_PITCH_HEAD(o), "pitchYINObj", dData, batch, dataLength, clipStride, dFre, hipStream, &T);
     if (go <= 0) return go;
     if (outStride < T) return AFX_ERR_ARG;
     AfxPitchYinArgs a;
@@ -175,7 +151,7 @@ int pitchYINObj_pitchBatchDevice(PitchYINObj o, const float *dData, int batch, i
 int pitchYINObj_troughsBatchDevice(PitchYINObj o, const float *dData, int batch, int dataLength, long long clipStride, float *dFre,
                                    float *dVal, int *dLen, int troughPitch, void *hipStream) {
     int T = 0;
-    const int go = batch_enter(o, dData, batch, dataLength, clipStride, dLen, hipStream, &T);
+    const int go = afx_pitch_batch_enter(AFX_PITCH_HEAD(o), "pitchYINObj", dData, batch, dataLength, clipStride, dLen, hipStream, &T);
     if (go <= 0) return go;
     if (troughPitch < 0 || (troughPitch > 0 && (!dFre || !dVal))) return AFX_ERR_ARG;
     AfxPitchYinArgs a;
@@ -190,7 +166,7 @@ int pitchYINObj_troughsBatchDevice(PitchYINObj o, const float *dData, int batch,
 int pitchYINObj_curveBatchDevice(PitchYINObj o, const float *dData, int batch, int dataLength, long long clipStride, float *dYin,
                                  void *hipStream) {
     int T = 0;
-    const int go = batch_enter(o, dData, batch, dataLength, clipStride, dYin, hipStream, &T);
+    const int go = afx_pitch_batch_enter(AFX_PITCH_HEAD(o), "pitchYINObj", dData, batch, dataLength, clipStride, dYin, hipStream, &T);
     if (go <= 0) return go;
     AfxPitchYinArgs a;
     fill_args(o, dData, batch, dataLength, clipStride, T, &a);
@@ -226,56 +202,44 @@ static int reserve_host(PitchYINObj o, int T) {
 }
 
 void pitchYINObj_pitch(PitchYINObj o, float *dataArr, int dataLength, float *freArr, float *valueArr1, float *valueArr2) {
-    AFX_ENTER(o);
+    static const char *who = "pitchYINObj_pitch";
     if (!o) {
-        afxdev_set_error("pitchYINObj_pitch: NULL object");
+        afxdev_set_error("%s: NULL object", who);
         return;
     }
-    if (!dataArr || dataLength <= 0) return; /* _pitch_yin.c:234-236 */
+    AfxPitchHead *h = &o->head;
+    AFX_ENTER(h);
     AfxFrameTake t;
-    const int T = afx_frametail_take(&o->tail, dataLength, &t);
-    o->timeLength = T > 0 ? T : 0;
-    if (T < 0) {
-        AFX_FAIL(o, T, "pitchYINObj_pitch");
-        return;
-    }
-    if (T == 0) {
-        afx_frametail_keep(&o->tail, dataArr, dataLength);
-        return;
-    }
+    const int T = afx_pitch_call_begin(h, dataArr, dataLength, &t, who);
+    if (T <= 0) return;
     const int n = t.total;
     int st = freArr ? AFX_OK : AFX_ERR_ARG;
     const int mLen = o->yinLength / 2 + 1;
     const size_t rowB = sizeof(float) * (size_t)T, candF = (size_t)T * (size_t)mLen;
     if (st == AFX_OK) st = reserve_host(o, T);
-    if (st == AFX_OK) st = afx_frametail_upload(&o->tail, &t, dataArr, &o->dX, &o->capX, o->stream);
-    if (st == AFX_OK) st = afxdev_reserve((void **)&o->dOut, &o->capOut, 3 * rowB);
+    if (st == AFX_OK) st = afx_frametail_upload(&h->tail, &t, dataArr, &h->dX, &h->capX, h->stream);
+    if (st == AFX_OK) st = afxdev_reserve((void **)&h->dOut, &h->capOut, 3 * rowB);
     if (st == AFX_OK) st = afxdev_reserve((void **)&o->dCand, &o->capCand, sizeof(float) * 2 * candF + sizeof(int) * (size_t)T);
     if (st == AFX_OK) {
         AfxPitchYinArgs a;
-        fill_args(o, o->dX, 1, n, n, T, &a);
-        a.fre = o->dOut;
-        a.trough = o->dOut + T;
-        a.minv = o->dOut + 2 * (size_t)T;
+        fill_args(o, h->dX, 1, n, n, T, &a);
+        a.fre = h->dOut;
+        a.trough = h->dOut + T;
+        a.minv = h->dOut + 2 * (size_t)T;
         a.outStride = T;
         a.candFre = o->dCand;
         a.candVal = o->dCand + candF;
         a.candLen = (int *)(o->dCand + 2 * candF);
         a.candPitch = mLen;
-        st = afxk_pitch_yin(&a, o->stream);
+        st = afxk_pitch_yin(&a, h->stream);
     }
-    if (st == AFX_OK) st = afxdev_d2h(o->hOut, o->dOut, 3 * rowB, o->stream);
-    if (st == AFX_OK) st = afxdev_d2h(o->lenArr, o->dCand + 2 * candF, sizeof(int) * (size_t)T, o->stream);
+    if (st == AFX_OK) st = afxdev_d2h(o->hOut, h->dOut, 3 * rowB, h->stream);
+    if (st == AFX_OK) st = afxdev_d2h(o->lenArr, o->dCand + 2 * candF, sizeof(int) * (size_t)T, h->stream);
     /* the kernel writes min(len, mLen) entries per frame; rows are fetched whole and the rest of a row is zeroed below */
-    if (st == AFX_OK) st = afxdev_d2h(o->mFreArr, o->dCand, sizeof(float) * candF, o->stream);
-    if (st == AFX_OK) st = afxdev_d2h(o->mTroughArr, o->dCand + candF, sizeof(float) * candF, o->stream);
-    if (st == AFX_OK) st = afxdev_stream_sync(o->stream);
-    afx_frametail_keep(&o->tail, dataArr, dataLength); /* the samples are taken in whatever becomes of the frames */
-    if (st != AFX_OK) {
-        o->timeLength = 0;
-        AFX_FAIL(o, st, "pitchYINObj_pitch");
-        return;
-    }
+    if (st == AFX_OK) st = afxdev_d2h(o->mFreArr, o->dCand, sizeof(float) * candF, h->stream);
+    if (st == AFX_OK) st = afxdev_d2h(o->mTroughArr, o->dCand + candF, sizeof(float) * candF, h->stream);
+    if (st == AFX_OK) st = afxdev_stream_sync(h->stream);
+    if (afx_pitch_call_end(h, dataArr, dataLength, st, who) != AFX_OK) return;
     for (int i = 0; i < T; ++i) {
         const float *h = o->hOut;
         if (h[i] != 0.f) { /* a found frequency is never 0: 0 marks "no trough", the caller's entries stay (_pitch_yin.c:548-551) */
@@ -300,21 +264,18 @@ int pitchYINObj_getTroughData(PitchYINObj o, float **mFreArr, float **mTroughArr
 
 void pitchYINObj_enableDebug(PitchYINObj o, int isDebug) {
     if (!o) return;
-    o->isDebug = isDebug;
+    o->head.isDebug = isDebug;
     if (isDebug)
         printf("pitchYIN params is: samplate=%d, fftLength=%d, slideLength=%d, autoLength=%d, minIndex=%d, maxIndex=%d, thresh=%g\n",
-               o->samplate, o->fftLength, o->slideLength, o->autoLength, o->minIndex, o->maxIndex, (double)o->thresh);
+               o->head.samplate, o->head.fftLength, o->head.slideLength, o->autoLength, o->minIndex, o->maxIndex, (double)o->thresh);
 }
 
 void pitchYINObj_free(PitchYINObj o) {
     if (!o) return;
-    if (o->stream) afxdev_stream_sync(o->stream);
+    afx_pitch_head_sync(&o->head);
     afxdev_free(o->dTwiddle);
-    afxdev_free(o->dX);
-    afxdev_free(o->dOut);
     afxdev_free(o->dCand);
-    if (o->stream) afxdev_stream_destroy(o->stream);
-    afx_frametail_free(&o->tail);
+    afx_pitch_head_release(&o->head);
     free(o->hOut);
     free(o->mFreArr);
     free(o->mTroughArr);
