@@ -12,6 +12,7 @@ from .spectral import Spectral
 from .cepstrogram import Cepstrogram
 from .cqt import CQT
 from .cwt import CWT
+from .fst import FST
 from .pwt import PWT
 from .nsgt import NSGT
 from .reassign import Reassign
@@ -25,7 +26,7 @@ from .spectrogram import (Bark, BarkSpectrogram, Chroma, Erb, ErbSpectrogram, Li
                           Spectrogram, SpectrogramBase, SpectralFilterBankType)
 from .batch import mel_mfcc_device
 
-__all__ = ["BFT", "XXCC", "Spectral", "SpectralNoveltyMethodType", "SpectralNoveltyDataType", "Cepstrogram", "CQT", "CWT", "PWT", "NSGT", "Reassign", "STFT", "HPSS", "median_filter_device", "Onset", "NoveltyParam", "NoveltyType", "power_to_db", "power_to_db_device",
+__all__ = ["BFT", "XXCC", "Spectral", "SpectralNoveltyMethodType", "SpectralNoveltyDataType", "Cepstrogram", "CQT", "CWT", "FST", "PWT", "NSGT", "Reassign", "STFT", "HPSS", "median_filter_device", "Onset", "NoveltyParam", "NoveltyType", "power_to_db", "power_to_db_device",
            "max_filter_device", "peak_pick_device", "PitchYIN", "PitchHPS", "PitchLHS", "PitchPEF", "Synsq", "WSST", "Spectrogram", "SpectrogramBase", "MelSpectrogram", "BarkSpectrogram", "ErbSpectrogram",
            "Linear", "Mel", "Bark", "Erb", "Chroma", "SpectralFilterBankType", "mel_mfcc_device", "get_lib", "build", "runtime_status",
            "last_error", "LIB_PATH"]

@@ -753,6 +753,37 @@ int afxk_onset_pick(const AfxOnsetPickArgs *a, void *stream);
  * allowed. */
 int afxk_power_to_db(const float *in, int batch, long long length, long long stride, float min, float *out, void *stream);
 
+/* ---- fast S-transform (afx_fst.hip) ----------------------------------------- */
+#define AFX_FST_MIN_EXP 4  /* the forward pass (afxk_nsgt_spectrum) starts at 2^4 */
+#define AFX_FST_MAX_EXP 14 /* the longest band, 2^12 points, is 33 KB of LDS */
+/* outputs of one launch above this many bytes are stored non-temporally: the L2 caches of the device hold 32 MB */
+#define AFX_FST_STREAM_BYTES (32ll << 20)
+typedef struct {
+    int r1, r2;              /* N = 2^(r1 + r2); frequency k of chunk c at Xt[c][k & (2^r1 - 1)][k >> r1]  */
+    const float *Xt;         /* device [chunks][N] complex: afxk_nsgt_spectrum's result                    */
+    const float *twiddle;    /* device float2 (cos, -sin)(2 pi m / N), m < N / 2: the forward pass's table  */
+    int chunks;              /* <= 65535 per launch                                                        */
+    float scale[16];         /* entry b: 1 / sqrt(N 2^b), the net scale of the band of 2^b points (0: singles) */
+    float *cellRe, *cellIm;  /* device [chunks][N / 2 + 1]: bin -1, DC, bin +1, band 2, band 4, ..., band N / 4 */
+} AfxFstCellArgs;
+/* the visible cells of every chunk: the three single bins as scaled copies, and per positive band of n = 2, 4, ..., N / 4
+ * points (bins n ... 2n - 1) its n-point inverse transform in LDS, the (-1)^k sign of the shifted spectrum and both
+ * half-rotations folded into the indices -- one launch, one workgroup per (band, chunk).  AFX_ERR_ARG for a NULL
+ * pointer or N outside 2^AFX_FST_MIN_EXP ... 2^AFX_FST_MAX_EXP, AFX_ERR_UNSUPPORTED for chunks > 65535. */
+int afxk_fst_cells(const AfxFstCellArgs *a, void *stream);
+typedef struct {
+    int radix2Exp;           /* N = 2^radix2Exp columns                                                    */
+    int minIndex, rows;      /* output row k shows index minIndex + k; 0 <= minIndex, minIndex + rows <= N / 2 + 1 */
+    int chunks;              /* <= 65535 per launch                                                        */
+    const int *rowMap;       /* device [N / 2 + 1][2]: (first cell, shift) of an index: column l holds cell first + (l >> shift) */
+    const float *cellRe, *cellIm; /* device [chunks][N / 2 + 1]                                            */
+    float *outRe, *outIm;    /* device [chunks][rows][N], any 4-byte alignment: every element is written   */
+} AfxFstExpandArgs;
+/* the sample-and-hold of the cells onto the N-column grid: each lane stores 4 consecutive columns of both planes (one
+ * value each: a cell repeats at least 4 times), 16 bytes a store where the plane is 16-byte aligned, dwords otherwise;
+ * non-temporal above AFX_FST_STREAM_BYTES.  AFX_ERR_ARG outside the limits above, AFX_ERR_UNSUPPORTED for chunks > 65535. */
+int afxk_fst_expand(const AfxFstExpandArgs *a, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

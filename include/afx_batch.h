@@ -33,6 +33,7 @@
 #include "mir/hpss_algorithm.h"
 #include "mir/onset_algorithm.h"
 #include "mir/_pitch_yin.h"
+#include "fst_algorithm.h"
 #include "nsgt_algorithm.h"
 #include "pwt_algorithm.h"
 #include "reassign_algorithm.h"
@@ -302,6 +303,12 @@ int afx_nsgt_plan_host(int num, int radix2Exp, int *samplate, float *lowFre, flo
                        SpectralFilterBankScaleType *filterScaleType, SpectralFilterBankStyleType *filterStyleType,
                        SpectralFilterBankNormalType *filterNormalType, int *lengthArr, int *offsetArr, int *binArr,
                        float *freArr, float *windowArr, int *maxLength, int *totalLength, int *colMapArr);
+
+/* ---- FST (fst_algorithm.h declares them beside the object) ----------------------------------------------------------------
+ *   int fstObj_getCellLength(FSTObj)                                   N/2 + 1 visible cells per chunk
+ *   int fstObj_fstBatchDevice(FSTObj, x, chunks, xStride, minIndex, maxIndex, outRe, outIm, cellRe, cellIm, stream)
+ *                                                                      matrix and / or cells of device-resident chunks
+ *   int afx_fst_plan_host(radix2Exp, rowCell, rowLen)                  the row -> cell map, without a device */
 
 #ifdef __cplusplus
 }
