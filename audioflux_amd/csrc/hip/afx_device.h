@@ -784,6 +784,25 @@ typedef struct {
  * non-temporal above AFX_FST_STREAM_BYTES.  AFX_ERR_ARG outside the limits above, AFX_ERR_UNSUPPORTED for chunks > 65535. */
 int afxk_fst_expand(const AfxFstExpandArgs *a, void *stream);
 
+/* ---- S-transform (afx_st.hip); sizes and the streaming threshold are the FST's -- */
+typedef struct {
+    int r1, r2;              /* N = 2^(r1 + r2); frequency k of chunk c at Xt[c][k & (2^r1 - 1)][k >> r1]  */
+    const float *Xt;         /* device [chunks][N] complex: afxk_nsgt_spectrum's result                    */
+    const float *twiddle;    /* device float2 (cos, -sin)(2 pi m / N), m < N / 2: the forward pass's table  */
+    const float *coef;       /* device [N / 2 + 1]: c_k = -factor 2 pi^2 / k^(2 norm) (entry 0 is not read) */
+    const int *bins;         /* device [rows]: the bin k of every output row, each in 0 ... N / 2          */
+    int rows;                /* 1 ... 2^31 - 1: one workgroup per (row, chunk)                              */
+    int chunks;              /* <= 65535 per launch                                                        */
+    float *outRe, *outIm;    /* device [chunks][rows][N], any 4-byte alignment: every element is written   */
+} AfxStArgs;
+/* row i of chunk c = ifft_j(X[(k + j) mod N] W_k[j]) with k = bins[i] and W_k[j] = expf(c_k j^2) + expf(c_k (j - N)^2)
+ * evaluated in the kernel (float: j^2 rounded, one multiply, expf, one add -- the sequence of st_algorithm.c:227-243); k = 0:
+ * Re X[0] / N in every column, zeros in the imaginary plane.  The N-point transform runs in LDS (afx_ldsfft.h, skewed:
+ * 8 afx_lds_padded_size(N) bytes, 135 KB at 2^14); 16 bytes a store where both planes are 16-byte aligned, dwords otherwise;
+ * non-temporal above AFX_FST_STREAM_BYTES.  AFX_ERR_ARG for a NULL pointer, rows <= 0 or N outside 2^AFX_FST_MIN_EXP ...
+ * 2^AFX_FST_MAX_EXP, AFX_ERR_UNSUPPORTED for chunks > 65535. */
+int afxk_st_rows(const AfxStArgs *a, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,7 @@
 #include "pwt_algorithm.h"
 #include "reassign_algorithm.h"
 #include "spectrogram_algorithm.h"
+#include "st_algorithm.h"
 #include "stft_algorithm.h"
 #include "synsq_algorithm.h"
 #include "wsst_algorithm.h"
@@ -309,6 +310,12 @@ int afx_nsgt_plan_host(int num, int radix2Exp, int *samplate, float *lowFre, flo
  *   int fstObj_fstBatchDevice(FSTObj, x, chunks, xStride, minIndex, maxIndex, outRe, outIm, cellRe, cellIm, stream)
  *                                                                      matrix and / or cells of device-resident chunks
  *   int afx_fst_plan_host(radix2Exp, rowCell, rowLen)                  the row -> cell map, without a device */
+
+/* ---- ST (st_algorithm.h declares them beside the object) ------------------------------------------------------------------
+ *   int stObj_getBinLength(STObj)                                      rows of the next call
+ *   int stObj_stBatchDevice(STObj, x, chunks, xStride, outRe, outIm, stream)
+ *                                                                      [chunks][binLength][N] of device-resident chunks
+ *   int afx_st_plan_host(radix2Exp, factor, norm, coef)                the window coefficients c_k, without a device */
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,63 @@
+"""CPU-only: the DEVICE code of audioflux_amd/csrc/hip/afx_st.hip compiled for the host (tests/emu/hip/hip_runtime.h: one
+thread per lane), linked with the C host objects and the generated stand-in for the rest of the device layer
+(tests/emu/emulated_st.py): the cases r4full, r6full, r9list and three rows of r9fn at the bar of the GPU tests, strided
+batches, guards, dword stores, setValue, refusals.  The spectrum is a float64 stand-in there: the arithmetic and indexing of
+k_st_rows are what this checks."""
+import os
+import subprocess
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EMU = os.path.join(ROOT, "tests", "emu")
+CLANG = "/opt/rocm/lib/llvm/bin/clang"
+INC = [f"-I{ROOT}/include", f"-I{ROOT}/audioflux_amd/csrc/hip", f"-I{ROOT}/audioflux_amd/csrc/host"]
+
+pytestmark = pytest.mark.skipif(not os.path.exists(CLANG), reason="needs clang")
+
+
+@pytest.fixture(scope="module")
+def emulated(tmp_path_factory):
+    tmp = str(tmp_path_factory.mktemp("emu_st"))
+    stub = os.path.join(tmp, "stub.c")
+    subprocess.run([sys.executable, os.path.join(ROOT, "tests", "hoststub", "gen_stub.py"),
+                    os.path.join(ROOT, "audioflux_amd", "csrc", "hip", "afx_device.h"), stub, "--omit=afxk_st_rows",
+                    "--omit=afxk_nsgt_spectrum"], check=True)
+    hostdir = os.path.join(ROOT, "audioflux_amd", "csrc", "host")
+    jobs = [["gcc", "-std=c99", "-O2", "-fPIC", "-ffp-contract=off", *INC, "-c", os.path.join(hostdir, f), "-o",
+             os.path.join(tmp, f[:-2] + "_c.o")] for f in sorted(os.listdir(hostdir)) if f.endswith(".c")]
+    jobs.append(["gcc", "-std=c99", "-O2", "-fPIC", *INC, "-c", stub, "-o", os.path.join(tmp, "stub.o")])
+    for f in ("emu_engine", "st_emulated"):
+        jobs.append([CLANG + "++", "-std=c++17", "-O2", "-g", "-fPIC", f"-I{EMU}", f"-I{EMU}/hip", *INC, "-c",
+                     os.path.join(EMU, f + ".cpp"), "-o", os.path.join(tmp, f + ".o")])
+    with ThreadPoolExecutor(8) as ex:
+        for r in ex.map(lambda c: subprocess.run(c, capture_output=True, text=True), jobs):
+            assert r.returncode == 0, r.stderr[-3000:]
+    lib = os.path.join(tmp, "libafx_emulated_st.so")
+    objs = sorted(os.path.join(tmp, f) for f in os.listdir(tmp) if f.endswith(".o"))
+    r = subprocess.run([CLANG + "++", "-shared", *objs, "-lm", "-lpthread", "-o", lib], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return lib
+
+
+def _run(lib, *what):
+    e = dict(os.environ, AFX_LIB=lib, AFX_QUIET="1")
+    r = subprocess.run([sys.executable, os.path.join(EMU, "emulated_st.py"), *what], capture_output=True, text=True, env=e,
+                       timeout=1500)
+    assert r.returncode == 0 and "\nOK" in r.stdout, (r.stdout + r.stderr)[-3000:]
+    return r.stdout
+
+
+def test_st_kernel_emulated_meets_the_references(emulated):
+    """k_st_rows through stObj_st and stObj_stBatchDevice: three inputs at the bar; the strided batch equals the single calls
+    bitwise; NaN pre-fill comes back finite; guards unchanged; dword stores; setValue to 1, 1 equals a fresh object"""
+    names = ("r4full", "r6full", "r9list", "r9fn")
+    out = _run(emulated, *names)
+    assert sum(line.startswith("st ") and "guards intact" in line for line in out.splitlines()) == len(names), out[-2000:]
+
+
+def test_st_refusals_and_bin_lists_emulated(emulated):
+    out = _run(emulated, "extras")
+    assert "refusals leave the outputs untouched" in out and "useBinArr rules" in out
