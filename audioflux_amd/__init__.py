@@ -20,7 +20,7 @@ from .st import ST
 from .stft import STFT
 from .hpss import HPSS, median_filter_device
 from .onset import NoveltyParam, Onset, max_filter_device, peak_pick_device, power_to_db, power_to_db_device
-from .pitch import PitchHPS, PitchLHS, PitchPEF, PitchYIN
+from .pitch import PitchCEP, PitchHPS, PitchLHS, PitchNCF, PitchPEF, PitchYIN
 from .synsq import Synsq
 from .wsst import WSST
 from .spectrogram import (Bark, BarkSpectrogram, Chroma, Erb, ErbSpectrogram, Linear, Mel, MelSpectrogram,
@@ -28,6 +28,6 @@ from .spectrogram import (Bark, BarkSpectrogram, Chroma, Erb, ErbSpectrogram, Li
 from .batch import mel_mfcc_device
 
 __all__ = ["BFT", "XXCC", "Spectral", "SpectralNoveltyMethodType", "SpectralNoveltyDataType", "Cepstrogram", "CQT", "CWT", "FST", "PWT", "NSGT", "Reassign", "ST", "STFT", "HPSS", "median_filter_device", "Onset", "NoveltyParam", "NoveltyType", "power_to_db", "power_to_db_device",
-           "max_filter_device", "peak_pick_device", "PitchYIN", "PitchHPS", "PitchLHS", "PitchPEF", "Synsq", "WSST", "Spectrogram", "SpectrogramBase", "MelSpectrogram", "BarkSpectrogram", "ErbSpectrogram",
+           "max_filter_device", "peak_pick_device", "PitchYIN", "PitchHPS", "PitchLHS", "PitchPEF", "PitchNCF", "PitchCEP", "Synsq", "WSST", "Spectrogram", "SpectrogramBase", "MelSpectrogram", "BarkSpectrogram", "ErbSpectrogram",
            "Linear", "Mel", "Bark", "Erb", "Chroma", "SpectralFilterBankType", "mel_mfcc_device", "get_lib", "build", "runtime_status",
            "last_error", "LIB_PATH"]

@@ -719,6 +719,38 @@ typedef struct {
  * in a launch. */
 int afxk_pitch_pef(const AfxPitchPefArgs *a, void *stream);
 
+/* ---- lag-domain pitch tracking: NCF and cepstrum (afx_pitch_lag.hip) -------- */
+#define AFX_PITCH_LAG_MIN_EXP 6
+#define AFX_PITCH_LAG_MAX_EXP 12 /* 13: a 16384-point complex buffer, 128 KB of LDS, one workgroup per CU */
+#define AFX_PITCH_LAG_NCF 0      /* curve from |X|^2: the normalised autocorrelation      */
+#define AFX_PITCH_LAG_CEP 1      /* curve from ln |X|^2: the real cepstrum                 */
+/* LDS bytes of a workgroup: cross-wave exchange and the 2N-point complex transform buffer (afx_ldsfft.h padding) */
+static inline long long afx_pitch_lag_lds_bytes(int radix2Exp) {
+    const long long n = 1LL << radix2Exp;
+    return 256 + 8 * (2 * n + (2 * n >> 5) + 1);
+}
+typedef struct {
+    const float *x;        /* device, clip b starts at x + b * clipStride                                         */
+    long long clipStride;  /* in samples                                                                          */
+    int batch, dataLength; /* clips, samples per clip                                                             */
+    int timeLength;        /* frames per clip: (dataLength - fftLength) / hop + 1 > 0                             */
+    int radix2Exp, hop;    /* N = fftLength = 2^radix2Exp, 6 ... 12; hop > 0 (may exceed fftLength)               */
+    int mode;              /* AFX_PITCH_LAG_NCF / AFX_PITCH_LAG_CEP                                               */
+    int samplate;          /* fre = samplate / (index + 1)                                                        */
+    int minIndex, maxIndex; /* candidates: 1 (CEP: 0) <= minIndex <= maxIndex <= N - 1 (CEP: 2N - 1)              */
+    const float *window;   /* device [N], or NULL: the rectangular window, no multiply                            */
+    const float *twiddle;  /* device float2 (cos, -sin)(2 pi m / 2N), m < N                                       */
+    float *fre, *value;    /* device [b * outStride + t] or NULL                                                  */
+    long long outStride;
+    float *curve;          /* device [row * (maxIndex + 1) + k], row = b * timeLength + t, or NULL                */
+} AfxPitchLagArgs;
+/* One launch from samples to results (_pitch_ncf.c:380-494, _pitch_cep.c:381-474): window, the 2N-point spectrum of the
+ * frame zero-padded to 2N, |X|^2 or ln |X|^2 in place, the inverse as a forward transform of that real, even sequence,
+ * NCF's normalisation by its own lag 0, the first argmax over minIndex ... maxIndex, fre = samplate / (index + 1).  One
+ * workgroup per frame; everything between the samples and the outputs stays in LDS and registers.  AFX_ERR_ARG for a plan
+ * outside the limits above, AFX_ERR_UNSUPPORTED beyond 2^31 - 1 frames in a launch. */
+int afxk_pitch_lag(const AfxPitchLagArgs *a, void *stream);
+
 /* ---- onset detection (afx_onset.hip) ---------------------------------------- */
 /* frames of one clip's envelope the picker keeps in LDS (32 KB: four workgroups of a CU keep theirs); a longer clip is
  * picked from global memory (the envelope the same workgroup wrote, or the caller's) */

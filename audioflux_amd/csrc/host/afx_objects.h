@@ -184,6 +184,23 @@ struct OpaquePitchPEF {
     float *dWindow, *dTwiddle, *dTaps, *dFilterSpec, *dLg; /* uploaded once: [N], [4N], [2N] taps, [2N + 1] float2, [2N] */
 };
 
+/* the lag-domain trackers: normalised autocorrelation and cepstrum (afx_pitch_lag.c, mir/_pitch_ncf.h, mir/_pitch_cep.h):
+ * one layout, `mode` selects the function of the spectrum */
+struct OpaquePitchLag {
+    AfxPitchHead head;
+    int mode;                /* AFX_PITCH_LAG_NCF / AFX_PITCH_LAG_CEP */
+    int minIndex, maxIndex;
+    float lowFre, highFre;
+    WindowType windowType;
+    float *dWindow, *dTwiddle; /* uploaded once: [N] (NULL for the rectangular window), [2N] */
+};
+struct OpaquePitchNCF {
+    struct OpaquePitchLag lag;
+};
+struct OpaquePitchCEP {
+    struct OpaquePitchLag lag;
+};
+
 /* the onset detector (afx_onset.c, mir/onset_algorithm.h) */
 struct OpaqueOnset {
     int noveltyType;         /* taken unchecked: anything that is not a named kind runs flux */

@@ -1,4 +1,4 @@
-"""PitchYIN, PitchHPS, PitchLHS, PitchPEF -- ctypes mirrors of the reference wrapper classes over libaudioflux_mi355x.so: same
+"""PitchYIN, PitchHPS, PitchLHS, PitchPEF, PitchNCF, PitchCEP -- ctypes mirrors of the reference wrapper classes over libaudioflux_mi355x.so: same
 constructor arguments and defaults, `cal_time_length`, `pitch`.  All leading axes of the input go through ONE batched call
 where the reference loops over channels.  Extra: device-resident calls on torch tensors.  `_Pitch` holds what every tracker
 shares; a new one supplies its constructor and, where its results differ from (fre, value) + curve, its own calls."""
@@ -268,3 +268,39 @@ class PitchPEF(_PitchFre):
         fn.argtypes = [c_void_p, c_float, c_float, c_float]
         fn(self._obj, alpha, beta, gamma)
         self.alpha, self.beta, self.gamma = alpha, beta, gamma
+
+
+class _PitchLag(_PitchFre):
+    """What PitchNCF and PitchCEP share (python/audioflux/mir/pitch_ncf.py:10-160, pitch_cep.py): `pitch` -> fre_arr,
+    samplate / (index + 1) of the first maximum of the lag-domain curve; column j of the curve is candidate index j."""
+
+    def __init__(self, samplate, low_fre, high_fre, radix2_exp, slide_length, window_type):
+        self.samplate, self.low_fre, self.high_fre = samplate, low_fre, high_fre
+        self.radix2_exp, self.slide_length, self.window_type = radix2_exp, slide_length, window_type
+        self.fft_length = 1 << radix2_exp
+        self.is_continue = False
+        self._new([POINTER(c_int), POINTER(c_float), POINTER(c_float), POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)],
+                  _util.opt_int(samplate), _util.opt_float(low_fre), _util.opt_float(high_fre), _util.opt_int(radix2_exp),
+                  _util.opt_int(slide_length), _util.opt_int(window_type), _util.opt_int(0))
+        self.min_index = self._get("minIndex")
+        self.max_index = self._get("maxIndex")
+
+
+class PitchNCF(_PitchLag):
+    """Normalised autocorrelation (include/mir/_pitch_ncf.h): curve[j] = (2N)^(-1/4) r[j + 1] / sqrt(r[0]) over min_index - 1
+    ... max_index - 1, r the inverse transform of the zero-padded frame's power spectrum.  Every window type is taken."""
+    _name = "NCF"
+
+    def __init__(self, samplate=32000, low_fre=32.0, high_fre=2000.0, radix2_exp=12, slide_length=1024, window_type=WindowType.RECT):
+        super().__init__(samplate, low_fre, high_fre, radix2_exp, slide_length, window_type)
+
+
+class PitchCEP(_PitchLag):
+    """Cepstrum (include/mir/_pitch_cep.h): curve[j] is the real cepstrum of the zero-padded frame at quefrency j.  A window
+    type above HAMM falls back to HAMM, as in the reference."""
+    _name = "CEP"
+
+    def __init__(self, samplate=32000, low_fre=32.0, high_fre=2000.0, radix2_exp=12, slide_length=1024, window_type=WindowType.HAMM):
+        if low_fre >= high_fre:  # (python/audioflux/mir/pitch_cep.py:72; pitch_ncf.py has no such check)
+            raise ValueError("`low_fre` must be smaller than `high_fre`")
+        super().__init__(samplate, low_fre, high_fre, radix2_exp, slide_length, window_type)
