@@ -5,8 +5,13 @@
 // wave talks to the LDS and what it no longer computes twice:
 //
 //   * every constant table is laid out for 16-byte reads: window and W_1024 twiddles as
-//     [(n1 >> 1)][lane][n1 & 1] (one ds_read_b128 = two rows), W_64 rows contiguous, the
-//     W_2048 split twiddles per lane [s][lane][m]                       (46 -> 22 table reads)
+//     [(n1 >> 1)][lane][n1 & 1] (one ds_read_b128 = two rows), the W_2048 split twiddles per lane
+//     [s][lane][m]                                                      (46 -> 22 table reads)
+//   * the W_64 twiddles are applied by the READER of exchange 2 (round 10): the second radix-16 stores its outputs as they
+//     are, and the lane that takes a base q into the last radix-4 multiplies V[q][1..3] by row j1 = q >> 4 of a 16-row
+//     table {W^j1, W^2j1 | W^3j1, pad} -- one ds_read_b128 + one ds_read_b64 per base, requested with the image rows; 12
+//     complex products per lane and frame where the writer had 15, 4 + 4 table reads (24 LDS cycles) where it had 8 x 16
+//     bytes (32) and a drain of its own.  The products are the same products: no power bin moves by a bit
 //   * exchange 1: row pitch 72 float2, writer lane 4 m1 + m2 stores at column
 //     8 (m1 >> 1) + 2 m2 + (m1 & 1): the reader takes (m1, m1 + 1) with one ds_read_b128;
 //     exchange 2: image V[q][m2] (m2 fastest; 16-byte halves swapped when bit 3 of q is set:
@@ -27,7 +32,8 @@
 //   * temporal features (TEMPORAL): energy / rms / zero-crossing rate of the windowed frame
 //     as wave reductions (temporal_algorithm.c:138-144), so isTemporal objects stay on this kernel
 //
-// Index algebra and LDS bank behaviour of every access class: tools/proto_fft1024_v2.py.
+// Index algebra and LDS bank behaviour of every access class: tools/proto_fft1024_v2.py; the W_64 table and its stage-3
+// reads: tools/proto_fft1024_v3.py.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -75,10 +81,11 @@ static_assert(16 * P1 * 8 <= PROW_OFF + 1025 * 4, "exchange image must end befor
 // table blob, byte offsets (built on the host by fill_tables + afxk_melfused_create, copied to LDS per workgroup)
 constexpr int T_WIN = 0;                     // [8][64] float4: (w[2n], w[2n+1]) of rows n1 = 2j, 2j + 1
 constexpr int T_TW1 = 8192;                  // [8][64] float4: W_1024^(lane k1), k1 = 2j, 2j + 1
-constexpr int T_TW2 = 16384;                 // [4] rows of 16 float2, TW2_PITCH bytes apart: W_64^(m2 j1)
-constexpr int TW2_PITCH = 144;               // (128 put rows m2 and m2 + 2 on the same banks: every read of this table two-way
-                                             //  conflicted -- the 6.4 % of the kernel's LDS cycles SQ_LDS_BANK_CONFLICT showed)
+constexpr int T_TW2 = 16384;                 // [16] rows j1 of 4 float2, TW2_PITCH bytes apart: W_64^(j1), W_64^(2 j1) | W_64^(3 j1), pad
+constexpr int TW2_PITCH = 32;                // (a row = 8 banks of 64; the lanes of one read group meet at most three rows, all within
+                                             //  one run of 8 consecutive rows: conflict-free, tools/proto_fft1024_v3.py)
 constexpr int T_TW3 = 16960;                 // [2][64][4] float2: 0.5 W_2048^bin of slot (s, lane, m)
+static_assert(TW2_PITCH % 16 == 0 && T_TW2 + 16 * TW2_PITCH <= T_TW3, "W_64 table: 16-byte rows, ends before the split twiddles");
 constexpr int T_BAND = 21056;                // [64][WP] floats: lane-major band weights, A then B taps (packed form: a | b | c)
 // (pc: the third partition of the packed form, 0 otherwise; the pitch stays an odd number of 16-byte units: conflict-free b128)
 __host__ __device__ constexpr int wpitch(int ta, int tb, int pc = 0) { return ta + tb + pc + 4; }
@@ -139,9 +146,11 @@ constexpr int STAMP_WORDS = 64, STAMP_HEAD = 8;  // t0, t1, workgroup | wave << 
 // AFX_PRIO_LEVEL.  The three waves of a SIMD are in different phases of their frames; with the transform's phases (1-4,
 // dense packed arithmetic between short LDS exchanges) above the window / band / store phases (LDS- and memory-latency
 // bound) a wave that can keep the vector unit busy wins the issue port: 1.53-1.56 -> 1.47-1.48 ms per step, measured
-// interleaved against masks 0x0A, 0x1F, 0x3E, 0x20, 0x61 and levels 1 / 2 / 3 (profiles/r04_ab_headline.txt).
+// interleaved against masks 0x0A, 0x1F, 0x3E, 0x20, 0x61 and levels 1 / 2 / 3 (profiles/r04_ab_headline.txt).  Round 10: phase 3
+// lost its table reads and their drain to phase 4 and is plain arithmetic + exchange stores now; with it at the base priority
+// (0x16) the step is 1.3 % shorter than with 0x1E, which the same mask on the round-9 kernel is not (profiles/r10_ab_headline.txt (e))
 #ifndef AFX_PRIO_MASK
-#define AFX_PRIO_MASK 0x1E
+#define AFX_PRIO_MASK 0x16
 #endif
 #ifndef AFX_PRIO_LEVEL
 #define AFX_PRIO_LEVEL 1
@@ -216,7 +225,6 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
     const int k1 = lane >> 2, m2 = lane & 3;
     const unsigned T0 = lds_addr(smem), W0 = lds_addr(wreg);
     const unsigned aWin = T0 + T_WIN + 16 * lane;                      // + 1024 j; W_1024 at + T_TW1
-    const unsigned aTw2 = T0 + T_TW2 + TW2_PITCH * m2;                       // + 16 j
     const unsigned aE1w = W0 + 8 * (8 * (k1 >> 1) + 2 * m2 + (k1 & 1));  // writer m1 = lane >> 2; row k: + 576 k
     const unsigned aE1r = W0 + 576 * k1 + 16 * m2;                     // pair jj: + 64 jj
     const unsigned aE2w = W0 + 32 * k1 + 16 * ((m2 >> 1) ^ ((k1 >> 3) & 1)) + 8 * (m2 & 1);  // j1: + 512 j1
@@ -225,6 +233,9 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
     const int qm0 = lane == 0 ? 128 : 256 - lane, qm1 = 192 - lane;
     const unsigned aB0lo = W0 + 32 * qm0 + 16 * ((qm0 >> 3) & 1), aB0hi = W0 + 32 * qm0 + 16 * (1 - ((qm0 >> 3) & 1));
     const unsigned aB1lo = W0 + 32 * qm1 + 16 * ((qm1 >> 3) & 1), aB1hi = W0 + 32 * qm1 + 16 * (1 - ((qm1 >> 3) & 1));
+    // W_64 rows of the four bases (row j1 = q >> 4): own bases lane, lane + 64 (s = 1: + 4 rows), mirror bases qm0, qm1
+    const unsigned aTwA = T0 + T_TW2 + TW2_PITCH * (lane >> 4);
+    const unsigned aTwB0 = T0 + T_TW2 + TW2_PITCH * (qm0 >> 4), aTwB1 = T0 + T_TW2 + TW2_PITCH * (qm1 >> 4);
     const unsigned aT3lo = T0 + T_TW3 + 32 * lane + 16 * b3l, aT3hi = T0 + T_TW3 + 32 * lane + 16 * (1 - b3l);
     const unsigned R = W0 + PROW_OFF;
     const unsigned aP01 = R + 4 * lane;                                // bins k, k + 256 | 64 + k ... by offsets
@@ -525,20 +536,14 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
             }
         }
 
-        // ---- 2b. radix-16 over m1, twiddle W_64^(m2 j1) -> image V[q = k1 + 16 j1][m2] --------
+        // ---- 2b. radix-16 over m1 -> image V[q = k1 + 16 j1][m2], NOT yet multiplied by W_64^(m2 j1): the reader of a base
+        //      q applies the three twiddles of its row j1 = q >> 4 (stage 3: 12 products per lane where the writer had 15) ----
         MEL_PHASE(3);
         if (!KO_ON(5)) dft16(v);
         {
-            v4f tq[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) RD128_S(2, tq[j], aTw2, 16 * j);
-            LDS_WAIT_N(0);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) PIN(tq[j]);
             v2 o[16];
-            o[0] = v[0];
 #pragma unroll
-            for (int j1 = 1; j1 < 16; ++j1) o[j1] = KO_ON(5) ? v[rev4(j1)] : cmul(v[rev4(j1)], (j1 & 1) ? hi2(tq[j1 >> 1]) : lo2(tq[j1 >> 1]));
+            for (int j1 = 0; j1 < 16; ++j1) o[j1] = v[rev4(j1)];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const unsigned b = aE2w + 2048 * g;  // j1 = 4g .. 4g+3, 512 bytes = 64 units apart
@@ -553,26 +558,63 @@ __global__ __launch_bounds__(waves_of(CPLX) * 64, 3) void k_stft_mel_v2(KArgs2 a
         float pk[2][4], pq[2][4], p512;  // |X|^2 (CPLX: real parts)
         float ik[CPLX ? 2 : 1][4], iq[CPLX ? 2 : 1][4], i512 = 0.f;  // CPLX: imaginary parts
         {
-            v4f zalo[2], zahi[2], zblo[2], zbhi[2], wlo[2], whi[2];
+            // per s: the two bases' image rows, their W_64 rows (16 + 8 bytes each: W^j1, W^2j1 | W^3j1) and the split twiddles --
+            // ten reads, all requested up front; s = 0 is waited for by count.  TAB_LATE (the STFT instantiations, whose
+            // stage 3 is their register peak: up front they spilled): the six table reads of s = 1 are requested behind the
+            // twiddle products of s = 0, whose W_64 rows are dead by then
+#ifdef AFX_V2_TABLATE  // (measurement: every instantiation; the headline is the same with it, profiles/r10_ab_headline.txt (e))
+            constexpr bool TAB_LATE = true;
+#else
+            constexpr bool TAB_LATE = STFT;
+#endif
+            v4f zalo[2], zahi[2], zblo[2], zbhi[2], wlo[2], whi[2], ta12[2], tb12[2];
+            v2 ta3[2], tb3[2];
+            auto tables_s1 = [&]() {
+                RD128_S(2, ta12[1], aTwA, 4 * TW2_PITCH);
+                RD64_S(2, ta3[1], aTwA, 4 * TW2_PITCH + 16);
+                RD128_S(2, tb12[1], aTwB1, 0);
+                RD64_S(2, tb3[1], aTwB1, 16);
+                RD128_S(2, wlo[1], aT3lo, 2048);
+                RD128_S(2, whi[1], aT3hi, 2048);
+            };
             RD128_S(1, zalo[0], aAlo, 0);
             RD128_S(1, zahi[0], aAhi, 0);
             RD128_S(1, zblo[0], aB0lo, 0);
             RD128_S(1, zbhi[0], aB0hi, 0);
+            RD128_S(2, ta12[0], aTwA, 0);
+            RD64_S(2, ta3[0], aTwA, 16);
+            RD128_S(2, tb12[0], aTwB0, 0);
+            RD64_S(2, tb3[0], aTwB0, 16);
             RD128_S(2, wlo[0], aT3lo, 0);
             RD128_S(2, whi[0], aT3hi, 0);
             RD128_S(1, zalo[1], aAlo, 2048);
             RD128_S(1, zahi[1], aAhi, 2048);
             RD128_S(1, zblo[1], aB1lo, 0);
             RD128_S(1, zbhi[1], aB1hi, 0);
-            RD128_S(2, wlo[1], aT3lo, 2048);
-            RD128_S(2, whi[1], aT3hi, 2048);
+            if constexpr (!TAB_LATE) tables_s1();
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                if (s == 0) LDS_WAIT_N(6);
+                if (s == 0) LDS_WAIT_N(TAB_LATE ? 4 : 10);
                 else LDS_WAIT_N(0);
                 PIN(zalo[s]); PIN(zahi[s]); PIN(zblo[s]); PIN(zbhi[s]); PIN(wlo[s]); PIN(whi[s]);
+                PIN(ta12[s]); PIN(ta3[s]); PIN(tb12[s]); PIN(tb3[s]);
                 v2 za0 = lo2(zalo[s]), za1 = hi2(zalo[s]), za2 = lo2(zahi[s]), za3 = hi2(zahi[s]);
                 v2 zb0 = lo2(zblo[s]), zb1 = hi2(zblo[s]), zb2 = lo2(zbhi[s]), zb3 = hi2(zbhi[s]);
+                if (!KO_ON(5)) {
+                    // V[q][m2] W_64^(m2 (q >> 4)), m2 = 1, 2, 3 (lane 0: row 0 of its base 0 holds (1, -0), base 128 has row 8)
+                    za1 = cmul(za1, lo2(ta12[s]));
+                    za2 = cmul(za2, hi2(ta12[s]));
+                    za3 = cmul(za3, ta3[s]);
+                    zb1 = cmul(zb1, lo2(tb12[s]));
+                    zb2 = cmul(zb2, hi2(tb12[s]));
+                    zb3 = cmul(zb3, tb3[s]);
+                }
+                if constexpr (TAB_LATE) {
+                    if (s == 0) {
+                        PIN(za1); PIN(za2); PIN(za3); PIN(zb1); PIN(zb2); PIN(zb3);  // (the products stand before the requests)
+                        tables_s1();
+                    }
+                }
                 dft4(za0, za1, za2, za3);  // Z[q + 256 j]
                 dft4(zb0, zb1, zb2, zb3);  // Z[q' + 256 j], q' the mirror base (lane 0, s = 0: 128)
                 v2 A0 = za0, A1 = za1, A2 = za2, A3 = za3;
@@ -771,12 +813,16 @@ void fill_tables(float *tab, const float *hWindow) {
             tw1[at] = (float)cos(ang);
             tw1[at + 1] = (float)sin(ang);
         }
-    for (int m = 0; m < 4; ++m)
-        for (int j = 0; j < 16; ++j) {
+    // W_64^(m j), m = 1, 2, 3, of the image rows V[q][m] with j = q >> 4: row j holds m = 1, 2 in its first 16 bytes, m = 3 and a
+    // pad in its second (row 0: (1, -0) three times, the values the writer-side table had in its column j = 0)
+    for (int j = 0; j < 16; ++j) {
+        for (int m = 1; m < 4; ++m) {
             const double ang = -2.0 * PI * (double)(m * j) / 64.0;
-            tw2[(TW2_PITCH / 4) * m + 2 * j] = (float)cos(ang);
-            tw2[(TW2_PITCH / 4) * m + 2 * j + 1] = (float)sin(ang);
+            tw2[(TW2_PITCH / 4) * j + 2 * (m - 1)] = (float)cos(ang);
+            tw2[(TW2_PITCH / 4) * j + 2 * (m - 1) + 1] = (float)sin(ang);
         }
+        tw2[(TW2_PITCH / 4) * j + 6] = tw2[(TW2_PITCH / 4) * j + 7] = 0.f;
+    }
     // 0.5 W_2048^bin of the P-bin of slot (s, lane, m); 16-byte halves swapped when bit 3 of lane is set
     for (int s = 0; s < 2; ++s)
         for (int l = 0; l < 64; ++l)
@@ -1002,6 +1048,16 @@ int launch_stft2k(const AfxStftArgs *a, const float *tab, void *stream) {
 const AfxMelSize *afx_mel_size2k() {
     static const AfxMelSize size = {11, 0, kVariants, 2, T_BAND, fill_tables, run, kPacks, 1, PROW_F};
     return &size;
+}
+
+// The transform's tables as the kernel copies them to LDS (no window): T_BAND bytes at `tab`, which holds `bytes`; returns T_BAND.
+// Host code, no device call.  Nothing on the host side calls it: tests/test_mel_tw2_cpu.py reads the W_64 rows at T_TW2 through it
+extern "C" int afxk_mel2k_tables(float *tab, int bytes) {
+    if (tab && bytes >= T_BAND) {
+        memset(tab, 0, T_BAND);
+        fill_tables(tab, nullptr);
+    }
+    return T_BAND;
 }
 
 // The n_fft 2048 wave transform storing its mapped spectrum rows (real results: |S|^2, |S|, |S|^2p) -- the [T, F] rows of the
