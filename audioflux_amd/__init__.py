@@ -16,6 +16,7 @@ from .fst import FST
 from .pwt import PWT
 from .nsgt import NSGT
 from .reassign import Reassign
+from .resample import Resample, WindowResample
 from .st import ST
 from .stft import STFT
 from .hpss import HPSS, median_filter_device
@@ -27,7 +28,7 @@ from .spectrogram import (Bark, BarkSpectrogram, Chroma, Erb, ErbSpectrogram, Li
                           Spectrogram, SpectrogramBase, SpectralFilterBankType)
 from .batch import mel_mfcc_device
 
-__all__ = ["BFT", "XXCC", "Spectral", "SpectralNoveltyMethodType", "SpectralNoveltyDataType", "Cepstrogram", "CQT", "CWT", "FST", "PWT", "NSGT", "Reassign", "ST", "STFT", "HPSS", "median_filter_device", "Onset", "NoveltyParam", "NoveltyType", "power_to_db", "power_to_db_device",
+__all__ = ["BFT", "XXCC", "Spectral", "SpectralNoveltyMethodType", "SpectralNoveltyDataType", "Cepstrogram", "CQT", "CWT", "FST", "PWT", "NSGT", "Reassign", "Resample", "WindowResample", "ResampleQualityType", "ST", "STFT", "HPSS", "median_filter_device", "Onset", "NoveltyParam", "NoveltyType", "power_to_db", "power_to_db_device",
            "max_filter_device", "peak_pick_device", "PitchYIN", "PitchHPS", "PitchLHS", "PitchPEF", "PitchNCF", "PitchCEP", "Synsq", "WSST", "Spectrogram", "SpectrogramBase", "MelSpectrogram", "BarkSpectrogram", "ErbSpectrogram",
            "Linear", "Mel", "Bark", "Erb", "Chroma", "SpectralFilterBankType", "mel_mfcc_device", "get_lib", "build", "runtime_status",
            "last_error", "LIB_PATH"]

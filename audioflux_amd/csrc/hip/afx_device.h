@@ -11,6 +11,7 @@
 #ifndef AFX_DEVICE_H
 #define AFX_DEVICE_H
 
+#include <math.h>
 #include <stddef.h>
 
 #ifdef __cplusplus
@@ -834,6 +835,97 @@ typedef struct {
  * non-temporal above AFX_FST_STREAM_BYTES.  AFX_ERR_ARG for a NULL pointer, rows <= 0 or N outside 2^AFX_FST_MIN_EXP ...
  * 2^AFX_FST_MAX_EXP, AFX_ERR_UNSUPPORTED for chunks > 65535. */
 int afxk_st_rows(const AfxStArgs *a, void *stream);
+
+/* ---- band-limited resampling (afx_resample.hip) ------------------------------ */
+#define AFX_RESAMPLE_TILE 512                  /* outputs of one work item = threads of a workgroup: a lane owns one output */
+#define AFX_RESAMPLE_GROUP 4                   /* clips of one work item at most: a weight is computed once for all of them */
+#define AFX_RESAMPLE_LDS_BUDGET (160 * 1024)   /* LDS one workgroup may declare on gfx950 */
+#define AFX_RESAMPLE_MAX_TABLE (1 << 24)       /* entries of the table a constructor accepts: 64 MB of device memory */
+/* what output i reads (resample_algorithm.c:483-511): the sample n under it, and per side the first table entry and the
+ * weight of the next one.  t is ONE float64 division rounded to float32, factor and scale - factor single float32
+ * roundings (no fused multiply-add: the pragma); factor * bitLength is exact, so offset and delta are. */
+typedef struct {
+    int n;               /* floorf(t), t = (float)(i / ratio): may reach sourceLength and beyond when dataLength * ratio rounded up */
+    int offL, offR;      /* first table entry of the left taps x[n - j] and of the right taps x[n + 1 + j] */
+    float deltaL, deltaR;
+} AfxResamplePhase;
+AFX_HD static inline AfxResamplePhase afx_resample_phase(long long i, float ratio, float scale, int bitLength) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    AfxResamplePhase p;
+    const float t = (float)((double)i / (double)ratio);
+    const float fn = floorf(t);
+    float factor = scale * (t - fn);
+    float fv = factor * (float)bitLength;
+    float fo = floorf(fv);
+    p.n = (int)fn;
+    p.offL = (int)fo;
+    p.deltaL = fv - fo;
+    factor = scale - factor;
+    fv = factor * (float)bitLength;
+    fo = floorf(fv);
+    p.offR = (int)fo;
+    p.deltaR = fv - fo;
+    return p;
+}
+/* min(1, ratio) and floorf(scale * bitLength): the table entries between two taps (resample_algorithm.c:455-456) */
+AFX_HD static inline float afx_resample_scale(float ratio) { return 1.0 > ratio ? ratio : 1.f; }
+AFX_HD static inline int afx_resample_step(float ratio, int bitLength) { return (int)floorf(afx_resample_scale(ratio) * (float)bitLength); }
+typedef struct {
+    const float *x;        /* device, clip b starts at x + b * clipStride                                         */
+    long long clipStride;  /* in samples, >= sourceLength when batch > 1                                          */
+    int batch;
+    int sourceLength;      /* samples per clip, > 0                                                               */
+    int targetLength;      /* outputs per clip, > 0                                                               */
+    float ratio;           /* targetRate / sourceRate as the object holds it; floorf(min(1, ratio) * bitLength) >= 1 */
+    int bitLength;         /* table entries per zero crossing, a power of two                                     */
+    int interpLength;      /* zeroNum * bitLength + 1                                                             */
+    const float *table;    /* device [interpLength + 1]: the table (times ratio when that is < 1), its last entry
+                            * repeated -- the difference table's last entry is 0 (resample_algorithm.c:543)       */
+    float outScale;        /* every output is divided by it: sqrtf(ratio) with isScale, else 1                    */
+    float *out;            /* device [b * outStride + i], i < targetLength: overwritten                           */
+    long long outStride;   /* >= targetLength when batch > 1                                                      */
+} AfxResampleArgs;
+/* What the launcher decides from the ratio and the table's size, without a device: where the table lives, how many clips a
+ * work item covers, how much of the input it stages. */
+typedef struct {
+    int tableInLds;       /* the table and its repeated last entry live in LDS                                    */
+    int group;            /* 1, 2 or AFX_RESAMPLE_GROUP clips per work item                                       */
+    int spanFloats;       /* staged input samples per clip (0: the taps read global memory)                       */
+    long long ldsBytes;   /* of one workgroup                                                                     */
+    int taps;             /* taps per side at most: interpLength / step                                           */
+} AfxResampleLaunch;
+static inline int afx_resample_launch_plan(int batch, float ratio, int bitLength, int interpLength, AfxResampleLaunch *l) {
+    const int step = afx_resample_step(ratio, bitLength);
+    if (step < 1 || interpLength < 2 || !(ratio > 0)) return AFX_ERR_ARG;
+    l->taps = interpLength / step;
+    const long long tabBytes = ((4ll * (interpLength + 1)) + 15) & ~15ll;
+    /* samples under one tile of outputs, both sides' taps, and slack for the float32 rounding of t near the tile's ends */
+    const double under = (double)(AFX_RESAMPLE_TILE - 1) / (double)ratio;
+    const double span = under + 2.0 * l->taps + 8.0;
+    l->tableInLds = tabBytes <= AFX_RESAMPLE_LDS_BUDGET;
+    const long long left = AFX_RESAMPLE_LDS_BUDGET - (l->tableInLds ? tabBytes : 0);
+    l->group = batch >= AFX_RESAMPLE_GROUP ? AFX_RESAMPLE_GROUP : (batch >= 2 ? 2 : 1);
+    l->spanFloats = 0;
+    if (4.0 * span <= (double)left) { /* one clip's span fits: as many clips as fit beside it */
+        const long long s = (((long long)span) + 3) & ~3ll;
+        while (l->group > 1 && 4 * s * l->group > left) l->group >>= 1;
+        if (4 * s * l->group <= left) l->spanFloats = (int)s;
+    }
+    if (!l->spanFloats) l->group = 1;
+    l->ldsBytes = (l->tableInLds ? tabBytes : 0) + 4ll * l->spanFloats * l->group;
+    if (l->ldsBytes < 16) l->ldsBytes = 16;
+    return AFX_OK;
+}
+/* Every output of every clip in one launch (resample_algorithm.c:430-521, the isScale division of :387-396 in the store):
+ * out[i] = sum over the left taps j < min(n + 1, (interpLength - offL) / step) of w x[n - j], then the right taps
+ * j < min(sourceLength - n - 1, (interpLength - offR) / step) of w x[n + 1 + j], with
+ * w = table[o] + delta (table[o + 1] - table[o]), o = off + j step, summed in float32 in that order.  Samples at
+ * n - j >= sourceLength count as 0 (the reference reads past its input there).  Persistent workgroups keep the table in
+ * LDS when it fits, else read it from global memory; the input span under a tile of outputs is staged in LDS when it fits.
+ * AFX_ERR_ARG for a NULL pointer, non-positive sizes, a stride below its row or a ratio with step < 1. */
+int afxk_resample(const AfxResampleArgs *a, void *stream);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,9 @@ float *afx_window_create(WindowType type, int length, int periodic);
  * family, symmetric for bartlett/triang/bartlett-hann/bohman) */
 float *afx_window_fft(WindowType type, int length);
 float *afx_window_kaiser(int length, float beta);
+/* symmetric Gauss / Tukey windows with an explicit alpha (the resampler table) */
+float *afx_window_gauss(int length, float alpha);
+float *afx_window_tukey(int length, float alpha);
 
 /* ---- afx_auditory.c ---------------------------------------------------- */
 /* fills bank[num*(fftLength/2+1)] (must be zeroed), fre[num], bin[num]; 0 or AFX_ERR_NOMEM */

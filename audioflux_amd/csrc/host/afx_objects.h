@@ -9,6 +9,7 @@
 #include "afx_pitchkit.h"
 #include "flux_base.h"
 #include "reassign_algorithm.h"
+#include "dsp/resample_algorithm.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -219,6 +220,18 @@ struct OpaqueOnset {
     int *dPoint;             /* [nLength + 1]: the points, then their count */
     size_t capIn, capPhase, capEvn, capPoint;
     AfxScratchStream scratchStream;
+    int status;
+};
+
+/* the resampler (afx_resample.c, dsp/resample_algorithm.h) */
+struct OpaqueResample {
+    AfxResamplePlan plan;    /* what the constructor and the rate setters decided; plan.table is interpArr, host,
+                              * [interpLength + 1]: the last entry repeated for the kernel's neighbour difference */
+    void *stream;
+    float *dTable;           /* [interpLength + 1], uploaded by the constructor and by every setter that rescales */
+    float *dX, *dOut;        /* grow-only device buffers of the host-pointer call */
+    size_t capX, capOut;
+    AfxScratchStream batchStream; /* of the last batched call: a setter drains it before the table changes */
     int status;
 };
 

@@ -34,6 +34,7 @@ typedef struct {
     float beta;     /* kaiser (no global state: constructors run concurrently on different threads) */
     float step;     /* bohman linspace step                             */
     int gauss_half; /* gauss: halfLen of its own mirrored construction  */
+    float alpha;    /* gauss, tukey */
 } WinCtx;
 
 /* h(i) for i in [0, half) -- one case per family */
@@ -95,7 +96,7 @@ static float half_value(WindowType type, const WinCtx *c, int i) {
             return (float)((1 - l) * cosf((float)(M_PI * l)) + 1 / M_PI * sinf((float)(M_PI * l)));
         }
         case Window_Gauss: { /* :718-736: stored reversed, alpha 2.5 */
-            const float a = 2.5f;
+            const float a = c->alpha;
             float det = (n & 1) ? 0.f : 0.5f;
             int k = c->gauss_half - 1 - i;
             float v = 2 * a * (k - det) / (n - 1);
@@ -108,21 +109,24 @@ static float half_value(WindowType type, const WinCtx *c, int i) {
 }
 
 /* symmetric window of length n into out[n] */
-static void fill_symmetric(WindowType type, int n, float *out, float kaiserBeta) {
+static void fill_symmetric(WindowType type, int n, float *out, float kaiserBeta, float alpha) {
     WinCtx c;
     c.n = n;
     c.beta = kaiserBeta;
+    c.alpha = alpha;
     c.den_i0 = 0;
     c.step = 0;
     c.gauss_half = 0;
     int half = (n & 1) ? (n + 1) / 2 : n / 2;
 
+    if (type == Window_Tukey && alpha == 0.f) type = Window_Rect; /* flux_window.c:586-595 */
+    if (type == Window_Tukey && alpha == 1.f) type = Window_Hann;
     if (type == Window_Rect) {
         for (int i = 0; i < n; i++) out[i] = 1.f;
         return;
     }
-    if (type == Window_Tukey) { /* flux_window.c:573-614, alpha 0.5 */
-        const float a = 0.5f;
+    if (type == Window_Tukey) { /* flux_window.c:573-614 */
+        const float a = alpha;
         float step = (1.f - 0.f) / (n - 1 > 0 ? n - 1 : 1);
         for (int i = 0; i < n; i++) {
             float x = 0.f + i * step;
@@ -150,7 +154,11 @@ static void fill_symmetric(WindowType type, int n, float *out, float kaiserBeta)
     for (int i = n - 1; i >= half; i--) out[i] = out[n - 1 - i];
 }
 
-static float *window_create_beta(WindowType type, int length, int periodic, float kaiserBeta) {
+#define AFX_GAUSS_ALPHA 2.5f
+#define AFX_TUKEY_ALPHA 0.5f
+static float family_alpha(WindowType type) { return type == Window_Tukey ? AFX_TUKEY_ALPHA : AFX_GAUSS_ALPHA; }
+
+static float *window_create_beta(WindowType type, int length, int periodic, float kaiserBeta, float alpha) {
     if (length <= 0) return NULL;
     float *w = (float *)calloc((size_t)length + 2, sizeof(float));
     if (!w) return NULL;
@@ -164,14 +172,14 @@ static float *window_create_beta(WindowType type, int length, int periodic, floa
         free(w);
         return NULL;
     }
-    fill_symmetric(type, n, tmp, kaiserBeta);
+    fill_symmetric(type, n, tmp, kaiserBeta, alpha);
     for (int i = 0; i < length; i++) w[i] = tmp[i];
     free(tmp);
     return w;
 }
 
 float *afx_window_create(WindowType type, int length, int periodic) {
-    return window_create_beta(type, length, periodic, AFX_KAISER_BETA);
+    return window_create_beta(type, length, periodic, AFX_KAISER_BETA, family_alpha(type));
 }
 
 float *afx_window_fft(WindowType type, int length) {
@@ -188,5 +196,17 @@ float *afx_window_fft(WindowType type, int length) {
 /* symmetric Kaiser window with an explicit beta (window_createKaiser(length, 0, &beta),
  * flux_window.c:112-127); used by the resampler table */
 float *afx_window_kaiser(int length, float beta) {
-    return window_create_beta(Window_Kaiser, length, 0, beta > 0 ? beta : AFX_KAISER_BETA);
+    return window_create_beta(Window_Kaiser, length, 0, beta > 0 ? beta : AFX_KAISER_BETA, 0.f);
+}
+
+/* symmetric Gauss window with an explicit alpha (window_createGauss(length, 0, &alpha), flux_window.c:180-194, 520-549:
+ * alpha <= 0 takes 2.5) */
+float *afx_window_gauss(int length, float alpha) {
+    return window_create_beta(Window_Gauss, length, 0, AFX_KAISER_BETA, alpha > 0 ? alpha : AFX_GAUSS_ALPHA);
+}
+
+/* symmetric Tukey window with an explicit alpha (window_createTukey(length, 0, &alpha), flux_window.c:265-279, 574-616:
+ * alpha outside 0 ... 1 takes 0.5, 0 is the rectangle, 1 the symmetric Hann window) */
+float *afx_window_tukey(int length, float alpha) {
+    return window_create_beta(Window_Tukey, length, 0, AFX_KAISER_BETA, alpha >= 0 && alpha <= 1 ? alpha : AFX_TUKEY_ALPHA);
 }

@@ -139,3 +139,10 @@ class NoveltyType(IntEnum):
     CD = 8
     RCD = 9
     BROADBAND = 10
+
+
+class ResampleQualityType(IntEnum):
+    """the Kaiser table of Resample (include/dsp/resample_algorithm.h)"""
+    BEST = 0
+    MID = 1
+    FAST = 2
