@@ -927,6 +927,50 @@ static inline int afx_resample_launch_plan(int batch, float ratio, int bitLength
  * AFX_ERR_ARG for a NULL pointer, non-positive sizes, a stride below its row or a ratio with step < 1. */
 int afxk_resample(const AfxResampleArgs *a, void *stream);
 
+/* ---- phase vocoder (afx_phasevocoder.hip) ------------------------------------- */
+/* Where output frame i sits between the input frames (phase_vocoder.c:36, :58-59): t = 0 + i * rate in float32 as
+ * __varange states it (flux_vector.c:2186), k = floorf(t), alpha = t - floorf(t).  Stated once for the kernels, the host
+ * plan and the tests. */
+AFX_HD static inline int afx_pv_time(int i, float rate, float *alpha) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float t = 0.f + (float)i * rate;
+    const float f = floorf(t);
+    *alpha = t - f;
+    return f < 2147483520.f ? (int)f : 2147483520; /* (beyond every frame count: a zero frame) */
+}
+/* output frames of T1 input frames: ceilf(T1 / rate) in float32 (phase_vocoder.c:35); 0: rate is not a positive finite
+ * number, or the count is beyond AFX_PV_MAX_FRAMES */
+#define AFX_PV_MAX_FRAMES (1 << 24)
+static inline int afx_pv_frames(int T1, float rate) {
+    if (T1 <= 0 || !(rate > 0.f) || !(rate <= 3.0e38f)) return 0;
+    const float f = ceilf((float)T1 / rate);
+    return f >= 1.f && f <= (float)AFX_PV_MAX_FRAMES ? (int)f : 0;
+}
+/* the expected phase advance of bin j per hop (phase_vocoder.c:38, __vlinspace flux_vector.c:2151-2158) */
+AFX_HD static inline float afx_pv_phi_step(int hop, int F) {
+    return ((float)(3.14159265358979323846 * hop) - 0.f) / (float)(F - 1 > 0 ? F - 1 : 1);
+}
+typedef struct {
+    const float *re, *im;  /* device [batch * T1, inPitch]: bins 0 ... N / 2 of every input frame are read                */
+    long long inPitch;     /* floats between input rows, >= N / 2 + 1                                                      */
+    int batch, T1, T2;     /* clips, input frames and output frames (afx_pv_frames) per clip                                */
+    int radix2Exp, hop;    /* N = 2^radix2Exp, 1 ... 14                                                                     */
+    float rate;
+    float *mag, *ang;      /* device scratch [batch * T1, N / 2 + 1] each; mag == re and ang == im (inPitch N / 2 + 1): in place */
+    float *outRe, *outIm;  /* device [batch * T2, N]: every word is written (outRe holds the phases between two launches)   */
+} AfxPhaseVocoderArgs;
+/* phase_vocoder.c:19-120 in three launches.  polar: mag = sqrtf(re re + im im) (unfused), ang = atan2f(im, re) of every input
+ * frame, once.  phase: one lane per (clip, bin j), serial over i < T2: phase[i][j] is stored to outRe[i][j], then advances by
+ * phi_j + wrap((ang[k + 1] - ang[k]) - phi_j) in float32, the wrap through float64 as the reference writes it; frames at or
+ * beyond T1 are zero frames (angle 0).  synthesis: (mag[k] (1 - alpha) + mag[k + 1] alpha) (cosf, sinf)(phase) over
+ * (clip, i, j), bin j and its conjugate mirror N - j.  AFX_ERR_ARG for a NULL pointer or sizes outside the limits above. */
+int afxk_phase_vocoder(const AfxPhaseVocoderArgs *a, void *stream);
+/* dst[b * dstStride + i] = i < srcLength ? src[b * srcStride + i] : 0 for i < length, b < batch: rows cut or zero-tailed */
+int afxk_rows_fit(const float *src, long long srcStride, int srcLength, float *dst, long long dstStride, int length, int batch,
+                  void *stream);
+
 #ifdef __cplusplus
 }
 #endif

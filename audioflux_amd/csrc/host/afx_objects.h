@@ -235,6 +235,36 @@ struct OpaqueResample {
     int status;
 };
 
+/* the time-stretch object (afx_timestretch.c, mir/timeStretch_algorithm.h) */
+struct OpaqueTimeStretch {
+    struct OpaqueSTFT *stft; /* owned: no padding, not continuing; its stream is the object's */
+    int radix2Exp, fftLength, slideLength;
+    long long scratchLimit;  /* bytes dScratch may grow to (one clip is always taken) */
+    void *stream;
+    float *dScratch;         /* grow-only chunk scratch: output spectrum re | im, half spectrum re | im, inverse transform */
+    size_t capScratch;
+    float *dX, *dOut;        /* grow-only device buffers of the host-pointer call */
+    size_t capX, capOut;
+    AfxScratchStream scratchStream;
+    int status;
+};
+
+/* the pitch-shift object (afx_pitchshift.c, mir/pitchShift_algorithm.h) */
+struct OpaquePitchShift {
+    struct OpaqueTimeStretch *stretch; /* owned; its stream is the object's */
+    struct OpaqueResample *resample;   /* owned: Fast, isScale 1 */
+    float lastRate;                    /* the ratio the resampler was last set to by this object (rateSet: it was set at all) */
+    int rateSet;
+    long long scratchLimit;
+    void *stream;
+    float *dScratch;         /* grow-only chunk scratch: stretched clips, resampled clips */
+    size_t capScratch;
+    float *dX, *dOut;
+    size_t capX, capOut;
+    AfxScratchStream scratchStream;
+    int status;
+};
+
 /* validated parameters of a BFT execution plan (afx_bft.c) */
 typedef struct {
     int num, radix2Exp, samplate;

@@ -32,6 +32,8 @@
 #include "feature/xxcc_algorithm.h"
 #include "mir/hpss_algorithm.h"
 #include "mir/onset_algorithm.h"
+#include "mir/pitchShift_algorithm.h"
+#include "mir/timeStretch_algorithm.h"
 #include "mir/_pitch_yin.h"
 #include "fst_algorithm.h"
 #include "nsgt_algorithm.h"
