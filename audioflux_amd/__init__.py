@@ -19,6 +19,7 @@ from .reassign import Reassign
 from .resample import Resample, WindowResample
 from .st import ST
 from .stft import STFT
+from .harmonic_ratio import HarmonicRatio
 from .hpss import HPSS, median_filter_device
 from .onset import NoveltyParam, Onset, max_filter_device, peak_pick_device, power_to_db, power_to_db_device
 from .pitchshift import PitchShift
@@ -30,7 +31,7 @@ from .spectrogram import (Bark, BarkSpectrogram, Chroma, Erb, ErbSpectrogram, Li
                           Spectrogram, SpectrogramBase, SpectralFilterBankType)
 from .batch import mel_mfcc_device
 
-__all__ = ["BFT", "XXCC", "Spectral", "SpectralNoveltyMethodType", "SpectralNoveltyDataType", "Cepstrogram", "CQT", "CWT", "FST", "PWT", "NSGT", "Reassign", "Resample", "WindowResample", "ResampleQualityType", "ST", "STFT", "HPSS", "median_filter_device", "Onset", "NoveltyParam", "NoveltyType", "power_to_db", "power_to_db_device",
+__all__ = ["BFT", "XXCC", "Spectral", "SpectralNoveltyMethodType", "SpectralNoveltyDataType", "Cepstrogram", "CQT", "CWT", "FST", "PWT", "NSGT", "Reassign", "Resample", "WindowResample", "ResampleQualityType", "ST", "STFT", "HarmonicRatio", "HPSS", "median_filter_device", "Onset", "NoveltyParam", "NoveltyType", "power_to_db", "power_to_db_device",
            "max_filter_device", "peak_pick_device", "PitchYIN", "PitchHPS", "PitchLHS", "PitchPEF", "PitchNCF", "PitchCEP", "PitchShift", "TimeStretch", "Synsq", "WSST", "Spectrogram", "SpectrogramBase", "MelSpectrogram", "BarkSpectrogram", "ErbSpectrogram",
            "Linear", "Mel", "Bark", "Erb", "Chroma", "SpectralFilterBankType", "mel_mfcc_device", "get_lib", "build", "runtime_status",
            "last_error", "LIB_PATH"]

@@ -752,6 +752,33 @@ typedef struct {
  * outside the limits above, AFX_ERR_UNSUPPORTED beyond 2^31 - 1 frames in a launch. */
 int afxk_pitch_lag(const AfxPitchLagArgs *a, void *stream);
 
+/* ---- harmonic ratio (afx_harmonic_ratio.hip) -------------------------------- */
+/* the window exponents are those of the lag kernel: the same L = 2N-point LDS transform, the same LDS bytes */
+#define AFX_HARMONIC_RATIO_NONE (-1) /* frames[row]: the frame found no zero crossing of its own */
+/* ints of the scratch a launch over `rows` frames needs: frames [rows], list [rows], count [1] */
+static inline long long afx_harmonic_ratio_scratch_ints(long long rows) { return 2 * rows + 1; }
+typedef struct {
+    const float *x;        /* device, clip b starts at x + b * clipStride                                         */
+    long long clipStride;  /* in samples                                                                          */
+    int batch, dataLength; /* clips, samples per clip                                                             */
+    int timeLength;        /* frames per clip: (dataLength - N) / hop + 1 > 0                                     */
+    int radix2Exp, hop;    /* N = windowLength = 2^radix2Exp, 6 ... 12; hop > 0 (may exceed N)                    */
+    int maxLength;         /* 2 <= maxLength <= N - 1: lags 1 ... maxLength - 1 are candidates                    */
+    const float *window;   /* device [N]                                                                          */
+    const float *twiddle;  /* device float2 (cos, -sin)(2 pi m / 2N), m < N                                       */
+    int *scratch;          /* device [afx_harmonic_ratio_scratch_ints(batch * timeLength)]                        */
+    float *value;          /* device [b * outStride + t] or NULL                                                  */
+    int *lag, *first;      /* device [b * outStride + t] or NULL: the chosen lag (-1: none), the minIndex used    */
+    long long outStride;
+    float *curve;          /* device [row * maxLength + j], row = b * timeLength + t, or NULL                     */
+} AfxHarmonicRatioArgs;
+/* Samples to results (harmonicRatio_algorithm.c:172-287) in three stream-ordered launches: every frame with its own first
+ * zero crossing (a frame without one assumes minIndex 0 and records NONE); per clip, the minIndex each such frame inherits
+ * from the nearest earlier frame that found one, and the list of frames for which that is not 0; those frames again with
+ * minIndex given.  One workgroup per frame in the first launch; everything between the samples and the outputs stays in
+ * LDS and registers.  AFX_ERR_ARG for a plan outside the limits above, AFX_ERR_UNSUPPORTED beyond 2^31 - 1 frames. */
+int afxk_harmonic_ratio(const AfxHarmonicRatioArgs *a, void *stream);
+
 /* ---- onset detection (afx_onset.hip) ---------------------------------------- */
 /* frames of one clip's envelope the picker keeps in LDS (32 KB: four workgroups of a CU keep theirs); a longer clip is
  * picked from global memory (the envelope the same workgroup wrote, or the caller's) */

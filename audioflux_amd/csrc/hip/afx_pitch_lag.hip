@@ -25,12 +25,7 @@
 namespace {
 
 template <int R>
-struct LagCfg {
-    static constexpr int L = 1 << R;
-    // threads: one radix-4 butterfly each per pass up to L = 4096, two at 8192.  A workgroup holds up to 66 KB of LDS, so a
-    // CU runs one or two of the large ones: the waves that hide LDS and barrier latency come from inside the workgroup
-    static constexpr int NT = L / 4 < 64 ? 64 : (L / 4 > 1024 ? 1024 : L / 4);
-};
+using LagCfg = AfxPitchLagCfg<R>;  // afx_pitchparts.h: shared with afx_harmonic_ratio.hip
 
 template <int R, int MODE>
 __global__ void __launch_bounds__(LagCfg<R>::NT) k_pitch_lag(AfxPitchLagArgs a) {

@@ -25,6 +25,15 @@ __device__ __forceinline__ const float *afx_pitch_row(const float *x, long long 
     return x + (long long)b * clipStride + (long long)t * hop;
 }
 
+// the workgroup of the kernels that transform L = 2^R complex points in LDS per frame (afx_pitch_lag.hip, afx_harmonic_ratio.hip)
+template <int R>
+struct AfxPitchLagCfg {
+    static constexpr int L = 1 << R;
+    // threads: one radix-4 butterfly each per pass up to L = 4096, two at 8192.  A workgroup holds up to 66 KB of LDS, so a
+    // CU runs one or two of the large ones: the waves that hide LDS and barrier latency come from inside the workgroup
+    static constexpr int NT = L / 4 < 64 ? 64 : (L / 4 > 1024 ? 1024 : L / 4);
+};
+
 // thread-local, indices visited in rising order: the FIRST maximum from minIndex on (a strict >)
 #define AFX_PITCH_CANDIDATE(bv, bi, c, j, minIndex)                          \
     if ((j) >= (minIndex) && ((bi) == AFX_PITCH_NONE || (c) > (bv))) {       \

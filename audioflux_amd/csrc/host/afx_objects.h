@@ -202,6 +202,18 @@ struct OpaquePitchCEP {
     struct OpaquePitchLag lag;
 };
 
+/* the harmonic ratio (afx_harmonic_ratio.c, mir/harmonicRatio_algorithm.h); head.fftLength is the WINDOW length N (the frame
+ * the call layer counts in), the transforms have 2N points */
+struct OpaqueHarmonicRatio {
+    AfxPitchHead head;
+    int maxLength;
+    float lowFre;
+    float *dWindow, *dTwiddle; /* uploaded once: [N], [2N] */
+    int *dScratch;           /* grow-only: afx_harmonic_ratio_scratch_ints(frames of a call) */
+    size_t capScratch;
+    AfxScratchStream scratchStream;
+};
+
 /* the onset detector (afx_onset.c, mir/onset_algorithm.h) */
 struct OpaqueOnset {
     int noveltyType;         /* taken unchecked: anything that is not a named kind runs flux */
